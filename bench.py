@@ -25,7 +25,15 @@ already resident in HBM:
             replica (control): full index per GPU, no collective.
 value = queries completed by all ranks / max-over-ranks wall time (weak scaling).
 
-    python bench.py [--gpus N --steps K --warmup W]
+A plain run does what the value needs and no more: it loads the index, makes
+the batches resident, warms up, times the K steps and prints the result line
+(--dump-outputs DIR: and writes the last timed step's results).  --full adds
+everything else the bench measures, each with runs of its own: the parity check
+against the oracle, the CPU baseline, the kernel accounting and roofline, the
+secondary legs (N = 1) and the other forms (N > 1).  --prepare builds the
+headline index and its log where a later run looks for them, and exits.
+
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 """
 import argparse
@@ -107,8 +115,35 @@ def log(msg):
     print(f"[bench] {msg}", file=sys.stderr, flush=True)
 
 
+def default_index_dir():
+    """Where the bench keeps its indexes: $WISER_BENCH_DIR, else the user's
+    cache directory (what __graft_entry__.build() prepared there is found by
+    every later run), else /tmp when there is no home to write to."""
+    d = os.environ.get("WISER_BENCH_DIR")
+    if d:
+        return d
+    cache = os.environ.get("XDG_CACHE_HOME") or os.path.join(os.path.expanduser("~"), ".cache")
+    probe = cache
+    while probe and not os.path.exists(probe):
+        probe = os.path.dirname(probe)
+    if os.path.isabs(cache) and probe and os.access(probe, os.W_OK):
+        return os.path.join(cache, "wiser_amd", "bench")
+    return "/tmp/wiser_bench"
+
+
 def parse():
     p = argparse.ArgumentParser()
+    p.add_argument("--full", action="store_true",
+                   help="besides the timed steps: the oracle parity check, the CPU baseline, the kernel "
+                        "accounting and roofline, the secondary legs (N = 1) and the other forms (N > 1); "
+                        "--no-cpu, --no-extra, --legs and --check choose among them")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write the results of the last timed step (what a caller "
+                        "of the batch receives: doc ids, scores, hit counts per query) as DIR/<name>.npy, "
+                        "float64")
+    p.add_argument("--prepare", action="store_true",
+                   help="build the headline index and its query log in --index-dir if they are missing, "
+                        "then exit (host only, no GPU work)")
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=3000,
                    help="timed steps (batches); the default makes the timed region >= 0.5 s")
@@ -132,7 +167,9 @@ def parse():
     p.add_argument("--dist-backend", default="gloo",
                    help="the launcher's host-side group (rendezvous, RCCL id, barriers, timing "
                         "reduction); the data path is the engine's own RCCL exchange")
-    p.add_argument("--index-dir", default=os.environ.get("WISER_BENCH_DIR", "/tmp/wiser_bench"))
+    p.add_argument("--index-dir", default=default_index_dir(),
+                   help="where the indexes and logs are kept (default: $WISER_BENCH_DIR, else "
+                        "wiser_amd/bench in the user's cache directory)")
     p.add_argument("--vacuum-dir", default=None,
                    help="configs[2]: an existing Vacuum dump (my.vacuum, my.tip, my.doc_length), "
                         "e.g. the reference's en-Wikipedia index, instead of the stand-in")
@@ -142,16 +179,16 @@ def parse():
     p.add_argument("--cpu-seconds", type=float, default=16.0,
                    help="bounded CPU-baseline sample (oracle), rank 0 at N=1, split over the "
                         "thread counts measured")
-    p.add_argument("--no-cpu", action="store_true")
+    p.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baselines")
     p.add_argument("--no-extra", action="store_true",
-                   help="skip the secondary legs (N=1 only)")
+                   help="--full: skip the secondary legs (N=1 only)")
     p.add_argument("--legs", default="",
                    help="comma list of secondary legs to run (default: all of c2_synthetic_1m, "
                         "end_to_end, c4_mixed_1to5, single_high, single_low, c5_phrase, realistic_mix, "
                         "c3_topics, serving, c1_snippets)")
     p.add_argument("--c3-docs", type=int, default=5_500_000)
     p.add_argument("--c3-term-scale", type=float, default=1.0)
-    p.add_argument("--check", type=int, default=256, help="queries checked against the oracle")
+    p.add_argument("--check", type=int, default=256, help="--full: queries checked against the oracle")
     p.add_argument("--max-inflight", type=int, default=0,
                    help="timed loops: before launching step s, wait until the batch of step s-K has "
                         "finished (K batches in flight at most; 0: no host throttle)")
@@ -172,7 +209,11 @@ def parse():
                         "one sharded step (a heavy batch every that many steps; 0, the default: "
                         "enough steps for about 4096 heavy queries per rank, at most the log's "
                         "batches)")
-    return p.parse_args()
+    a = p.parse_args()
+    if not a.full:   # a plain run: the timed steps only
+        a.no_cpu = a.no_extra = True
+        a.check = 0
+    return a
 
 
 def c3_dir(a):
@@ -286,6 +327,29 @@ def resolve(eng, chunk, k):
     for i, terms in enumerate(chunk):
         arr[i] = eng.resolve(w.SearchQuery(terms, n_results=k))[0]
     return arr
+
+
+def result_arrays(hits, nh, nq, k, prefix=""):
+    """A batch's fetched results as float64 arrays, for --dump-outputs: doc ids
+    and scores [nq, k] (slots past a query's hit count: -1 and 0) and the hit
+    counts [nq].  Copies: the batch's own arrays are reused by its next fetch."""
+    import numpy as np
+    rec = np.frombuffer(hits, dtype=[("doc_id", "<i4"), ("pad", "<i4"), ("score", "<f8")], count=nq * k)
+    counts = np.frombuffer(nh, dtype="<i4", count=nq).astype(np.float64)
+    held = np.arange(k)[None, :] < counts[:, None]
+    return {prefix + "doc_ids": np.where(held, rec["doc_id"].reshape(nq, k), -1).astype(np.float64),
+            prefix + "scores": np.where(held, rec["score"].reshape(nq, k), 0.0).astype(np.float64),
+            prefix + "hit_counts": counts}
+
+
+def write_outputs(d, arrays, rank, world):
+    """--dump-outputs: DIR/<name>.npy (N > 1: DIR/<name>_rank<r>.npy, each
+    rank its own queries' results)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    tail = f"_rank{rank}" if world > 1 else ""
+    for name, arr in arrays.items():
+        np.save(os.path.join(d, f"{name}{tail}.npy"), arr)
 
 
 def check_against_oracle(idx, chunk, hits, nh, k, n, phrase=False):
@@ -1153,9 +1217,15 @@ def run_shard(a, S, full, heavy_blocks, lines, rank, world, dist):
         comm = {k: cs1[k] - cs0[k] for k in cs1}
         comm["mean_group"] = round(comm["steps"] / max(1, comm["groups"]), 3)
     snaps = []
+    outputs = {}
     for i, (hb, hq, hchunk, cb, cheap) in enumerate(steps):   # error flags (a slot overflow among
         hres = S.fetch_owned(hb, hq) if hb else None         # them) of every last step
         cres = cb.fetch() if cb else None
+        if a.dump_outputs and a.steps > 0 and i == (a.steps - 1) % nb:   # the last timed step's batches
+            if hres:
+                outputs.update(result_arrays(hres[0], hres[1], hq, a.k, "sharded_"))
+            if cres:
+                outputs.update(result_arrays(cres[0], cres[1], len(cheap), a.k, "whole_"))
         if i == 0 and a.check and rank == 0:   # step 0's last timed run, checked after the timed loops
             if hres:
                 snaps.append(snapshot(S.engine.engine_dir_path, hchunk[:hq], hres[0], hres[1], a.k, a.check))
@@ -1172,7 +1242,7 @@ def run_shard(a, S, full, heavy_blocks, lines, rank, world, dist):
             for x in (hb, cb):
                 if x:
                     x.close()
-    return {"queries": queries, "el": el, "p50": statistics.median(lat), "snaps": snaps,
+    return {"queries": queries, "el": el, "p50": statistics.median(lat), "snaps": snaps, "outputs": outputs,
             "slot": slot, "heavy_share": share, "heavy_blocks": heavy_blocks, "every": every,
             "host_ms": host_ms, "comm": comm,
             "batches": [st[3] for st in steps if st[3]] or [st[0] for st in steps if st[0]],
@@ -1217,11 +1287,15 @@ def run_replica(a, eng, idx, lines, rank, world, dist):
     host_ms = (time.perf_counter() - t0) / max(1, a.steps) * 1e3
     w.sync(eng)
     el = time.perf_counter() - t0
-    timed_launch_stats(batches, a.steps)
+    if a.full:
+        timed_launch_stats(batches, a.steps)
     # every batch's last run: the device error flags (capacity, limits) must be
     # clear, or the pass does not count (fetch raises on any flag)
-    for b in batches[::-1]:
-        hits, nh = b.fetch()
+    outputs = {}
+    for i in range(nb - 1, -1, -1):
+        hits, nh = batches[i].fetch()
+        if a.dump_outputs and a.steps > 0 and i == (a.steps - 1) % nb:   # the last timed step's batch
+            outputs = result_arrays(hits, nh, batches[i].nq, a.k)
     snaps = []
     if a.check and rank == 0:   # batch 0's last timed run, checked after every timed loop
         snaps.append(snapshot(idx, chunks[0], hits, nh, a.k, a.check))
@@ -1230,7 +1304,7 @@ def run_replica(a, eng, idx, lines, rank, world, dist):
     def close():
         for b in batches:
             b.close()
-    return {"queries": queries, "el": el, "p50": statistics.median(lat), "snaps": snaps,
+    return {"queries": queries, "el": el, "p50": statistics.median(lat), "snaps": snaps, "outputs": outputs,
             "host_ms": host_ms, "batches": batches, "engine": eng, "close": close}
 
 
@@ -1324,6 +1398,10 @@ def spawn_ranks(gpus, argv, script=None):
 
 def main():
     a = parse()
+    if a.prepare:
+        idx, qlog, _ = ensure_index(a, 0, None)
+        log(f"index {idx} and log {qlog} are in place")
+        return
     # before any HIP call (runtime_info below is one): N > 1 without a launcher
     # spawns one, and a launcher whose world size is not N is refused
     if check_world(a.gpus, os.environ) == "spawn":
@@ -1376,7 +1454,7 @@ def main():
         hb_default = max(64, 63 * world)
         S = open_shard_engine(a, idx, rank, world, local, dist, threads)
         shard_bytes = S.engine.image_info()["total_bytes"]
-        if world > 1 and a.mode == "auto" and a.heavy_blocks != 0:
+        if a.full and world > 1 and a.mode == "auto" and a.heavy_blocks != 0:
             # the pure doc-range form first, with only this rank's shard image
             # resident: the form an index larger than one GPU runs, and its own
             # HBM per rank
@@ -1402,18 +1480,21 @@ def main():
         share = main_run["heavy_share"]
         parallelism = (f"docshard{world}" if hb == 0 else
                        f"hybrid-docshard{world} ({100 * share:.2f}% of queries sharded)")
-    acc = kernel_accounting(main_run["engine"], main_run["batches"])
+    if a.dump_outputs:
+        write_outputs(a.dump_outputs, main_run["outputs"], rank, world)
     image = main_run["engine"].image_info()
-    nbk = len(main_run["batches"])
-    iso_ms = acc["seg"] / nbk
-    seg_avg_ms = DIAG.get("timed_seg_ms", iso_ms)
-    seg_src = "timed region" if "timed_seg_ms" in DIAG else "one batch at a time"
-    lean_avg_ms = DIAG.get("timed_lean_ms", acc["lean"] / nbk)
+    if a.full:
+        acc = kernel_accounting(main_run["engine"], main_run["batches"])
+        nbk = len(main_run["batches"])
+        iso_ms = acc["seg"] / nbk
+        seg_avg_ms = DIAG.get("timed_seg_ms", iso_ms)
+        seg_src = "timed region" if "timed_seg_ms" in DIAG else "one batch at a time"
+        lean_avg_ms = DIAG.get("timed_lean_ms", acc["lean"] / nbk)
     mres = reduced(main_run)
     snaps = main_run["snaps"]
     host_ms = main_run["host_ms"]
     main_run["close"]()
-    if world > 1 and a.mode == "auto":
+    if a.full and world > 1 and a.mode == "auto":
         # the control, from the same full image: replicas (no collective)
         r = run_replica(a, full, idx, lines, rank, world, dist)
         forms["replica"] = {**reduced(r), "parallelism": f"replicas{world}", "hbm_per_rank": full_bytes,
@@ -1438,30 +1519,31 @@ def main():
         cpu = cpu_baseline(idx, lines, a.k, a.cpu_seconds, "the headline workload's log")
 
     if rank == 0:
-        # the dominant kernel, lean_kernel (its HIP events on the batch stream,
-        # plan end -> lean end; the general segment_kernel runs beside it on a
-        # second stream and is given with the fork -> join time below)
-        roof = roofline_of(acc, nbk, lean_avg_ms, seg_src + ", lean_kernel (HIP events on its stream)",
-                           "lean_kernel")
-        roof.update({"traffic": None, "traffic_source": None})
-        if mode == "replica":
-            pmc = load_pmc(wkey)
-            if pmc:
-                roof.update(pmc)
-        roof.update({
-            # the same bytes over the pipelined step time (consecutive batches
-            # overlap on the device; value's own clock)
-            "achieved_per_step": round((acc["algo"] / nbk) / (mres["seconds"] / a.steps) / 1e9, 1),
-            # the segment phase: lean_kernel with the general segment_kernel
-            # beside it on a second stream (HIP events fork -> join on the
-            # batch's stream; isolated: one batch at a time, nothing overlapping)
-            "lean_kernel_ms": round(lean_avg_ms, 4),
-            "fork_join_ms": round(seg_avg_ms, 4),
-            "frac_fork_join": round((acc["algo"] / nbk) / (seg_avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-            "isolated_launch_ms": round(iso_ms, 4),
-            "isolated_frac": round((acc["algo"] / nbk) / (iso_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-            "algo_bytes_rule": "SURVEY 8d: per query the docid+tf span bytes of every term's list "
-                               "(wsr_list_bytes) + 1 B per survivor + 12 B per result"})
+        if a.full:
+            # the dominant kernel, lean_kernel (its HIP events on the batch stream,
+            # plan end -> lean end; the general segment_kernel runs beside it on a
+            # second stream and is given with the fork -> join time below)
+            roof = roofline_of(acc, nbk, lean_avg_ms, seg_src + ", lean_kernel (HIP events on its stream)",
+                               "lean_kernel")
+            roof.update({"traffic": None, "traffic_source": None})
+            if mode == "replica":
+                pmc = load_pmc(wkey)
+                if pmc:
+                    roof.update(pmc)
+            roof.update({
+                # the same bytes over the pipelined step time (consecutive batches
+                # overlap on the device; value's own clock)
+                "achieved_per_step": round((acc["algo"] / nbk) / (mres["seconds"] / a.steps) / 1e9, 1),
+                # the segment phase: lean_kernel with the general segment_kernel
+                # beside it on a second stream (HIP events fork -> join on the
+                # batch's stream; isolated: one batch at a time, nothing overlapping)
+                "lean_kernel_ms": round(lean_avg_ms, 4),
+                "fork_join_ms": round(seg_avg_ms, 4),
+                "frac_fork_join": round((acc["algo"] / nbk) / (seg_avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                "isolated_launch_ms": round(iso_ms, 4),
+                "isolated_frac": round((acc["algo"] / nbk) / (iso_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                "algo_bytes_rule": "SURVEY 8d: per query the docid+tf span bytes of every term's list "
+                                   "(wsr_list_bytes) + 1 B per survivor + 12 B per result"})
         out = {
             "metric": METRIC, "value": mres["value"], "unit": "queries/s", "n_gpus": world,
             "steps": a.steps, "warmup": a.warmup, "ms_per_step": mres["ms_per_step"],
@@ -1474,15 +1556,19 @@ def main():
             "p50_ms": (extra["end_to_end"]["p50_ms"] if extra and "end_to_end" in extra
                        else mres["p50_alone_ms"]),
             "p50_alone_ms": mres["p50_alone_ms"],
-            "roofline": roof,
-            "cpu_baseline": cpu,
-            "kernel_ms_per_batch": {"plan": round(acc["plan"] / nbk, 4),
-                                    "segment": round(iso_ms, 4),
-                                    "replay": round(acc["rep"] / nbk, 4)},
-            "per_batch": {"survivors": int(acc["surv"] / nbk), "driver_blocks": int(acc["dblk"] / nbk),
-                          "other_blocks": int(acc["oblk"] / nbk), "work_items": int(acc["items"] / nbk)},
-            "parity_checked_queries": checked,
+            "full": a.full,
         }
+        if a.full:
+            out.update({
+                "roofline": roof,
+                "cpu_baseline": cpu,
+                "kernel_ms_per_batch": {"plan": round(acc["plan"] / nbk, 4),
+                                        "segment": round(iso_ms, 4),
+                                        "replay": round(acc["rep"] / nbk, 4)},
+                "per_batch": {"survivors": int(acc["surv"] / nbk), "driver_blocks": int(acc["dblk"] / nbk),
+                              "other_blocks": int(acc["oblk"] / nbk), "work_items": int(acc["items"] / nbk)},
+                "parity_checked_queries": checked,
+            })
         out["runtime"] = runtime
         out["image"] = image   # HBM bytes of the engine image the value ran on
         out["load_s"] = load_s

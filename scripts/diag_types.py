@@ -8,16 +8,17 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import wiser_amd as w
 from wiser_amd import _capi
+from bench import default_index_dir
 
 import argparse
 ap = argparse.ArgumentParser()
-ap.add_argument("--index", default="/tmp/wiser_bench/c2_1000000_500000")
+ap.add_argument("--index", default=os.path.join(default_index_dir(), "c2_1000000_500000"))
 ap.add_argument("--only", default="")
 ap.add_argument("--repeat", type=int, default=1)
 ap.add_argument("--wiki", action="store_true", help="the C3 stand-in (bench.py c3_leg's index)")
 args = ap.parse_args()
 if args.wiki and args.index == ap.get_default("index"):
-    args.index = "/tmp/wiser_bench/c3_wiki_5500000_1"
+    args.index = os.path.join(default_index_dir(), "c3_wiki_5500000_1")
 idx = args.index
 if not os.path.exists(os.path.join(idx, "READY")):
     os.makedirs(idx, exist_ok=True)

@@ -11,7 +11,7 @@ mkdir -p "$O" "$P"
 export TMPDIR=/tmp
 cd /tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$P/stats" -o stats -- \
-    python3 "$R/bench.py" --no-cpu --no-extra --steps 2000 > "$O/bench_stats.json" 2> "$O/bench_stats.err"
+    python3 "$R/bench.py" --full --no-cpu --no-extra --steps 2000 > "$O/bench_stats.json" 2> "$O/bench_stats.err"
 find "$P/stats" -name "*kernel_stats.csv" -exec cp {} "$O/kernel_stats.csv" \;
 find "$P/stats" -name "*kernel_trace.csv" -exec cp {} "$P/kernel_trace.csv" \;
 python3 "$R/scripts/trace_overlap.py" "$P/kernel_trace.csv" > "$O/trace_overlap.json"
@@ -23,7 +23,7 @@ for counters in "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_128B_sum TCC_EA0_RDREQ_32B_sum"
   timeout -s KILL 120 rocprofv3 --pmc $counters --output-format csv -d "$P/calib/pass$i" -o pmc -- \
       "$R/wiser_amd/_lib/calib_ea" > "$O/calib_pass$i.json" 2> "$O/calib_pass$i.err"
   timeout -k 10 600 rocprofv3 --pmc $counters --output-format csv -d "$P/pmc/pass$i" -o pmc -- \
-      python3 "$R/bench.py" --no-cpu --no-extra --check 0 --steps 5 --warmup 1 > "$O/pmc_pass$i.json" 2> "$O/pmc_pass$i.err"
+      python3 "$R/bench.py" --full --no-cpu --no-extra --check 0 --steps 5 --warmup 1 > "$O/pmc_pass$i.json" 2> "$O/pmc_pass$i.err"
   echo "pmc pass $i ok"
 done
 python3 "$R/scripts/pmc_bytes.py" "$P/calib" > "$O/calib_bytes.txt"
@@ -33,6 +33,6 @@ python3 "$R/scripts/pmc_bytes.py" "$P/pmc" > "$O/pmc_all_kernels.txt"
 echo done
 # the sharded path rehearsed with one rank: where a step's time goes
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$P/shard" -o shard -- \
-    python3 "$R/bench.py" --mode shard --no-cpu --no-extra --steps 300 > "$O/shard_stats.json" 2> "$O/shard_stats.err"
+    python3 "$R/bench.py" --full --mode shard --no-cpu --no-extra --steps 300 > "$O/shard_stats.json" 2> "$O/shard_stats.err"
 find "$P/shard" -name "*kernel_stats.csv" -exec cp {} "$O/shard_kernel_stats.csv" \;
 echo "shard stats ok"

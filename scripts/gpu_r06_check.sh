@@ -20,12 +20,12 @@ tail -3 "$O/pytest_gpu.log"
 timeout -k 10 120 python3 -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1
 cat "$O/smoke.log"
 if [ $N8 = 1 ]; then
-  timeout -k 10 900 python3 bench.py --gpus 8 --exchange gloo --workload c2 --docs 200000 --vocab 100000 \
+  timeout -k 10 900 python3 bench.py --full --gpus 8 --exchange gloo --workload c2 --docs 200000 --vocab 100000 \
       --queries 40000 --steps 40 --warmup 4 --no-extra --no-cpu --check 128 --index-dir /tmp/wiser_n8 \
       > "$O/n8_gloo.json" 2> "$O/n8_gloo.err"
   tail -c 1200 "$O/n8_gloo.json"; echo
 fi
-timeout -k 10 900 python3 bench.py --steps 20 --warmup 5 "$@" > "$O/bench.json" 2> "$O/bench.err"
+timeout -k 10 900 python3 bench.py --full --steps 20 --warmup 5 "$@" > "$O/bench.json" 2> "$O/bench.err"
 python3 - "$O/bench.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

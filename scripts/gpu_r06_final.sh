@@ -8,7 +8,7 @@ O=$R/gpurun_out/r06z
 mkdir -p "$O"
 cd "$R"
 for i in 1 2; do
-  timeout -k 10 900 python3 bench.py --steps 20 --warmup 5 > "$O/bench_$i.json" 2> "$O/bench_$i.err"
+  timeout -k 10 900 python3 bench.py --full --steps 20 --warmup 5 > "$O/bench_$i.json" 2> "$O/bench_$i.err"
   python3 - "$O/bench_$i.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

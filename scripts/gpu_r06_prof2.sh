@@ -12,6 +12,6 @@ cd "$R"
 bash scripts/gpu_prof_legs.sh r06p c4_mixed_1to5 c5_phrase single_high realistic_mix
 export TMPDIR=/tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/wsr_benchprof -o bench -- \
-    python3 "$R/bench.py" --steps 20 --warmup 5 --no-extra --no-cpu > "$O/bench_under_rocprof.json" 2> "$O/bench_under_rocprof.err"
+    python3 "$R/bench.py" --full --steps 20 --warmup 5 --no-extra --no-cpu > "$O/bench_under_rocprof.json" 2> "$O/bench_under_rocprof.err"
 find /tmp/wsr_benchprof -name "*kernel_stats.csv" -exec cp {} "$O/bench_kernel_stats.csv" \;
 echo "bench under rocprof ok"

@@ -23,7 +23,7 @@ if [ $DIAG = 1 ]; then
   timeout -k 10 600 python3 -u scripts/diag_classes.py > "$O/diag.txt" 2> "$O/diag.err"
   cat "$O/diag.txt"
 fi
-timeout -k 10 900 python3 bench.py --steps 20 --warmup 5 "$@" > "$O/bench.json" 2> "$O/bench.err"
+timeout -k 10 900 python3 bench.py --full --steps 20 --warmup 5 "$@" > "$O/bench.json" 2> "$O/bench.err"
 python3 - "$O/bench.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -12,15 +12,15 @@ P=/tmp/wsr_shprof_$TAG
 mkdir -p "$O" "$P"
 export TMPDIR=/tmp
 cd "$R"
-WSR_HOST_TIMING=1 timeout -k 10 400 python3 bench.py --mode shard --heavy-blocks 0 --no-extra --no-cpu \
+WSR_HOST_TIMING=1 timeout -k 10 400 python3 bench.py --full --mode shard --heavy-blocks 0 --no-extra --no-cpu \
     --steps 1000 "$@" > "$O/shard_hb0.json" 2> "$O/shard_hb0.err"
 grep -h "wsr_shard_step host" "$O/shard_hb0.err" || true
-WSR_HOST_TIMING=1 timeout -k 10 400 python3 bench.py --mode shard --no-extra --no-cpu \
+WSR_HOST_TIMING=1 timeout -k 10 400 python3 bench.py --full --mode shard --no-extra --no-cpu \
     --steps 1000 "$@" > "$O/shard_hybrid.json" 2> "$O/shard_hybrid.err"
 grep -h "wsr_shard_step host" "$O/shard_hybrid.err" || true
 cd /tmp
 timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$P/hb0" -o hb0 -- \
-    python3 "$R/bench.py" --mode shard --heavy-blocks 0 --no-extra --no-cpu --steps 300 "$@" \
+    python3 "$R/bench.py" --full --mode shard --heavy-blocks 0 --no-extra --no-cpu --steps 300 "$@" \
     > "$O/prof_hb0.json" 2> "$O/prof_hb0.err"
 find "$P/hb0" -name "*kernel_stats.csv" -exec cp {} "$O/hb0_kernel_stats.csv" \;
 find "$P/hb0" -name "*kernel_trace.csv" -exec cp {} "$P/hb0_trace.csv" \;
@@ -32,7 +32,7 @@ echo "hb0 trace ok"
 # pure doc-range, replicas), host exchange pipelined behind the next step
 cd "$R"
 timeout -k 10 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-    --master-port 29517 bench.py --gpus 2 --exchange gloo --steps 400 --warmup 20 --no-cpu "$@" \
+    --master-port 29517 bench.py --full --gpus 2 --exchange gloo --steps 400 --warmup 20 --no-cpu "$@" \
     > "$O/n2_gloo.json" 2> "$O/n2_gloo.err"
 python3 - "$O/n2_gloo.json" <<'PY'
 import json, sys

@@ -10,14 +10,15 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import wiser_amd as w  # noqa: E402
 from wiser_amd import _capi  # noqa: E402
+from bench import default_index_dir  # noqa: E402
 
 
 def index(c2):
     if c2:
-        idx = "/tmp/wiser_bench/c2_1000000_500000"
+        idx = os.path.join(default_index_dir(), "c2_1000000_500000")
         build = lambda: w.build_synthetic(idx, threads=16)  # noqa: E731
     else:
-        idx = "/tmp/wiser_bench/c3_wiki_5500000_1"
+        idx = os.path.join(default_index_dir(), "c3_wiki_5500000_1")
         build = lambda: w.build_wiki_standin(idx, n_docs=5_500_000, term_scale=1.0, threads=16)  # noqa: E731
     log = os.path.join(idx, "two_term_100000.log")
     if not os.path.exists(os.path.join(idx, "READY")):

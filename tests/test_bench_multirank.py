@@ -32,7 +32,7 @@ def test_bench_two_ranks_gloo(built, tmp_path):
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--exchange", "gloo", "--workload", "c2",
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--exchange", "gloo", "--workload", "c2",
            "--docs", "50000", "--vocab", "50000", "--queries", "20000", "--steps", "20", "--warmup", "2",
            "--no-extra", "--no-cpu", "--check", "64", "--index-dir", str(tmp_path)]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=400, env=env, cwd=ROOT)
@@ -57,7 +57,7 @@ def test_bench_gpus2_spawns_its_launcher(built, tmp_path):
     one-rank measurement."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--exchange", "gloo",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--exchange", "gloo",
            "--workload", "c2", "--docs", "50000", "--vocab", "50000", "--queries", "20000", "--steps", "20",
            "--warmup", "2", "--no-extra", "--no-cpu", "--check", "64", "--mode", "shard", "--heavy-blocks", "0",
            "--index-dir", str(tmp_path)]

@@ -17,6 +17,20 @@ import make_writer_sha as mws  # noqa: E402
 GOLDEN = json.load(open(os.path.join(HERE, "golden", "writer_sha256.json")))
 
 
+@pytest.fixture(autouse=True, scope="module")
+def _open_files():
+    """The merge holds every run file open: a chunk of 1 row cuts the 10k-row
+    fixture into 10k runs, more than the usual soft limit of 1024 descriptors
+    (the hard limit allows them), so the soft limit is raised for this module."""
+    import resource
+    soft, hard = resource.getrlimit(resource.RLIMIT_NOFILE)
+    want = 16384 if hard == resource.RLIM_INFINITY else min(hard, 16384)
+    if soft != resource.RLIM_INFINITY and soft < want:
+        resource.setrlimit(resource.RLIMIT_NOFILE, (want, hard))
+    yield
+    resource.setrlimit(resource.RLIMIT_NOFILE, (soft, hard))
+
+
 def _build_env(chunk, threads):
     import wiser_amd as w
 
