@@ -45,6 +45,7 @@ extern "C" {
 #define WSR_MAX_TERMS 16        /* terms held in wsr_query.list_ids (more: wsr_query.more_ids) */
 #define WSR_MAX_QUERY_TERMS 1024 /* terms of a conjunctive query (AOL's longest query has 245) */
 #define WSR_MAX_PHRASE_TERMS 8  /* terms of a phrase query (the reference's cap, query_processing.h:695) */
+#define WSR_MAX_OR_TERMS 16     /* terms of a disjunctive query (WSR_QUERY_OR): the ids held inline */
 #define WSR_MAX_K 1024          /* n_results (k > 64 keeps the replay's heap in LDS) */
 #define WSR_SERVER_MAX_K WSR_MAX_K  /* n_results through the micro-batcher (wsr_server_*) */
 
@@ -53,7 +54,8 @@ enum {
   WSR_E_INVALID = -1,   /* bad argument */
   WSR_E_IO = -2,        /* missing / malformed index files */
   WSR_E_HIP = -3,       /* HIP runtime error (no device, out of memory, ...) */
-  WSR_E_LIMIT = -4,     /* n_terms > WSR_MAX_QUERY_TERMS (phrase: WSR_MAX_PHRASE_TERMS) or k > WSR_MAX_K */
+  WSR_E_LIMIT = -4,     /* n_terms > WSR_MAX_QUERY_TERMS (phrase: WSR_MAX_PHRASE_TERMS, disjunctive:
+                           WSR_MAX_OR_TERMS) or k > WSR_MAX_K */
   WSR_E_INTERNAL = -5
 };
 
@@ -83,13 +85,26 @@ typedef struct wsr_query {
   int32_t flags;      /* WSR_QUERY_PHRASE: SearchQuery::is_phrase (types.h:205-256) --
                          a doc is ranked only if the terms occur at consecutive
                          positions (QueryProcessor::HandleTheFoundDoc,
-                         query_processing.h:854-912); needs positions at wsr_open */
+                         query_processing.h:854-912); needs positions at wsr_open.
+                         WSR_QUERY_OR: a disjunctive query (beyond the reference, which
+                         has none) -- a doc matches when it is in the list of at least one
+                         term; a term not in the index (-1) contributes nothing instead of
+                         emptying the result (any other id outside the index's lists is
+                         WSR_E_INVALID at upload); the score is the f64 sum, from 0.0 and in
+                         query order, of the BM25 terms of the lists that hold the doc
+                         (a term given twice counts twice), so a doc that holds every
+                         term scores its conjunctive score bit for bit; ranking is
+                         RankDoc over the matching docs in ascending doc id, then
+                         SortHeap, as for every query.  At most WSR_MAX_OR_TERMS terms;
+                         not with WSR_QUERY_PHRASE (WSR_E_INVALID); no snippets and no
+                         doc-range shard steps (both WSR_E_INVALID) */
   const int32_t* more_ids;   /* n_terms > WSR_MAX_TERMS: list ids of terms 16 .. n_terms - 1
                                 (caller's memory, read during the call that takes the
                                 query; the reference's conjunctive processor has no
                                 term cap, query_processing.h:710-728,810-852) */
 } wsr_query;
 #define WSR_QUERY_PHRASE 1
+#define WSR_QUERY_OR 2
 
 typedef struct wsr_hit {
   int32_t doc_id;
@@ -106,7 +121,8 @@ typedef struct wsr_hit {
  * the mapped index, the text from the doc store (my.fdx / my.fdt,
  * ChunkedDocStoreReader, doc_store.h:365-455; WSR_E_INVALID if the index has
  * none).  Writes min(len, cap) bytes to out (no terminator) and the full
- * length to *len. */
+ * length to *len.  A WSR_QUERY_OR query has no snippets (WSR_E_INVALID here and
+ * in wsr_snippets_batch): the highlighter takes a bag of every term in the doc. */
 int wsr_snippet(wsr_handle* h, const wsr_query* q, int32_t doc_id, int32_t n_passages,
                 char* out, int32_t cap, int32_t* len);
 /* The snippets of a batch's result entries, built by `threads` host threads
@@ -142,7 +158,10 @@ typedef struct wsr_batch_stats {
   uint64_t algo_bytes;       /* sum over queries of docid+tf span bytes of its lists (a phrase
                                 query: + the lists' position boxes) + survivors * 1 B + k * 12 B
                                  */
-  double plan_ms, segment_ms, replay_ms;  /* HIP-event times on the engine stream */
+  double plan_ms, segment_ms, replay_ms;  /* HIP-event times on the engine stream; replay_ms (the
+                                             launches after the segment kernels have joined) also
+                                             spans the traversal and replay of the batch's
+                                             WSR_QUERY_OR queries, which run there */
   uint64_t events;           /* segment heap-insertion events handed to the replay */
   uint64_t max_query_events; /* the largest per-query event count of the batch */
   double lean_ms;            /* lean_kernel alone (segment_ms spans it and the concurrent
@@ -218,7 +237,9 @@ int wsr_search_text(wsr_handle* h, const char* text, int64_t len, int32_t k, int
  * size of the first class.  Batches cut from this order are class-pure: a
  * phrase query's position check then runs in batches of its own instead of
  * riding, a few hundred at a time, at the tail of every conjunctive batch
- * (DESIGN.md §4i).  Needs no handle. */
+ * (DESIGN.md §4i).  Disjunctive queries (WSR_QUERY_OR) come last, after the
+ * phrase queries, in their stream order; *n_conj does not count them.  Needs
+ * no handle. */
 int wsr_class_order(const wsr_query* q, int32_t nq, int32_t* order, int32_t* n_conj);
 
 /* ---- resident batches ------------------------------------------------ */
@@ -235,6 +256,15 @@ int wsr_sync(wsr_handle* h);
  * flag (hits / n_hits then hold no meaningful results). */
 int wsr_batch_fetch(wsr_handle* h, wsr_batch* b, wsr_hit* hits, int32_t* n_hits);
 int wsr_batch_stats_get(wsr_handle* h, wsr_batch* b, wsr_batch_stats* out);
+/* Counters of the disjunctive (WSR_QUERY_OR) queries of the batch's last run
+ * (all 0 when it held none): their work items; the 2,048-doc accumulator
+ * windows those ran; the windows jumped over by MaxScore skipping while a
+ * non-essential list still had postings there (k <= 64 only); the docs that
+ * got a score; the events handed to the replay. */
+typedef struct wsr_or_stats {
+  uint64_t items, windows, windows_skipped, touched_docs, events;
+} wsr_or_stats;
+int wsr_batch_or_stats_get(wsr_handle* h, wsr_batch* b, wsr_or_stats* out);
 /* as wsr_batch_fetch, but only the first `cols` (<= hit stride) entries of each
  * query: hits is nq x cols (a pitched copy; cols >= every query's k) */
 int wsr_batch_fetch_cols(wsr_handle* h, wsr_batch* b, wsr_hit* hits, int32_t* n_hits, int32_t cols);
@@ -290,7 +320,9 @@ int wsr_server_bench(wsr_server* s, const wsr_query* q, int32_t nq, int32_t n_cl
  * DESIGN.md, "Why replaying events is exact").  A region = the {count, offset}
  * pairs of the owner's q_per_owner queries, padded to whole 16-byte events,
  * then a slot of `slot` events; a query whose events overflow the slot is
- * flagged (count -1 and an error flag that wsr_batch_fetch* reports). */
+ * flagged (count -1 and an error flag that wsr_batch_fetch* reports).
+ * Disjunctive queries are not sharded: every shard step call fails with
+ * WSR_E_INVALID, before anything is enqueued, on a batch that holds one. */
 /* results of the batch's queries [q0, q0 + nq) (an owner's slice) */
 int wsr_batch_fetch_range(wsr_handle* h, wsr_batch* b, int32_t q0, int32_t nq, wsr_hit* hits,
                           int32_t* n_hits);
@@ -386,7 +418,10 @@ int wsr_shard_step_emit_async(wsr_handle* h, wsr_batch* b, int32_t world, int32_
 int wsr_batch_stream_sync(wsr_handle* h, wsr_batch* b);
 /* Driver blocks per work item at most for this batch's runs (1..63, default
  * 63): shorter items cut a batch's latency (its longest item) at some cost in
- * throughput; the serving front end's batches use WSR_SERVER_ITEM_BLOCKS. */
+ * throughput; the serving front end's batches use WSR_SERVER_ITEM_BLOCKS.
+ * The items of disjunctive queries are cut by wsr_batch_upload: for them the
+ * setting in force at the upload counts (about that many blocks over all the
+ * query's lists per item). */
 int wsr_batch_set_item_blocks(wsr_handle* h, wsr_batch* b, int32_t blocks);
 
 /* Decode one block of a list on the device (test hook for the decoder):

@@ -29,6 +29,9 @@ struct SearchQuery {  // types.h:205-256
   bool return_snippets = false;  // entries get snippets (host stage, wsr_snippet)
   int n_snippet_passages = 3;
   bool is_phrase = false;        // >= 2 terms: consecutive positions required (WSR_QUERY_PHRASE)
+  bool match_any = false;        // disjunctive (WSR_QUERY_OR): the docs that hold any of the terms; a
+                                 // missing term contributes nothing (doc_freq 0); not with is_phrase
+                                 // or return_snippets
 };
 
 struct SearchResultEntry {  // types.h:259-274
@@ -104,17 +107,21 @@ class VacuumHipEngine {
       const SearchQuery& q = qs[i];
       if (q.terms.size() > WSR_MAX_QUERY_TERMS || q.n_results > WSR_MAX_K)
         throw std::runtime_error("query over the engine limits");
+      if (q.match_any && (q.is_phrase || q.return_snippets))
+        throw std::runtime_error("wiser_hip: match_any goes with neither is_phrase nor return_snippets");
+      if (q.match_any && q.terms.size() > WSR_MAX_OR_TERMS)
+        throw std::runtime_error("wiser_hip: more than WSR_MAX_OR_TERMS terms in a match_any query");
       wsr_query& w = in[i];
       w.more_ids = nullptr;
       w.k = q.n_results < 0 ? 0 : q.n_results;
-      w.flags = (q.is_phrase && q.terms.size() > 1) ? WSR_QUERY_PHRASE : 0;
+      w.flags = q.match_any ? WSR_QUERY_OR : (q.is_phrase && q.terms.size() > 1) ? WSR_QUERY_PHRASE : 0;
       bool missing = q.terms.empty();
       for (size_t t = 0; t < q.terms.size(); ++t) {
         int32_t id, df;
         check(wsr_lookup(h_, q.terms[t].c_str(), &id, &df));
         if (t < WSR_MAX_TERMS) w.list_ids[t] = id;
         else more[i].push_back(id);
-        if (id < 0) missing = true;
+        if (id < 0 && !q.match_any) missing = true;
         freqs[i].push_back(df);
       }
       if (!more[i].empty()) w.more_ids = more[i].data();

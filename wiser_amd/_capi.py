@@ -18,6 +18,7 @@ HEADER = os.path.join(os.path.dirname(HERE), "include", "wiser_hip.h")
 MAX_TERMS = 16            # terms held in Query.list_ids (more: Query.more_ids)
 MAX_QUERY_TERMS = 1024
 MAX_PHRASE_TERMS = 8
+MAX_OR_TERMS = 16         # terms of a disjunctive query (QUERY_OR)
 MAX_K = 1024
 SERVER_MAX_K = MAX_K
 
@@ -28,6 +29,7 @@ ERRORS = {-1: "WSR_E_INVALID", -2: "WSR_E_IO", -3: "WSR_E_HIP", -4: "WSR_E_LIMIT
 
 
 QUERY_PHRASE = 1
+QUERY_OR = 2              # a doc matches when it holds at least one of the terms
 
 
 class OpenOpts(C.Structure):
@@ -51,6 +53,11 @@ class BatchStats(C.Structure):
                 ("segment_ms", C.c_double), ("replay_ms", C.c_double),
                 ("events", C.c_uint64), ("max_query_events", C.c_uint64),
                 ("lean_ms", C.c_double)]
+
+
+class OrStats(C.Structure):
+    _fields_ = [("items", C.c_uint64), ("windows", C.c_uint64), ("windows_skipped", C.c_uint64),
+                ("touched_docs", C.c_uint64), ("events", C.c_uint64)]
 
 
 class ImageInfo(C.Structure):
@@ -118,6 +125,7 @@ _sigs = {
     "wsr_sync": (C.c_int, [_P]),
     "wsr_batch_fetch": (C.c_int, [_P, _P, C.POINTER(Hit), C.POINTER(C.c_int32)]),
     "wsr_batch_stats_get": (C.c_int, [_P, _P, C.POINTER(BatchStats)]),
+    "wsr_batch_or_stats_get": (C.c_int, [_P, _P, C.POINTER(OrStats)]),
     "wsr_batch_fetch_range": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(Hit),
                                         C.POINTER(C.c_int32)]),
     "wsr_stream": (C.c_int, [_P, C.POINTER(_P)]),

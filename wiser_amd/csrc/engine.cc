@@ -198,6 +198,21 @@ struct wsr_batch {
   int x_world = 0, x_qpr = 0;   // ... for this world and q_per_owner
   int64_t x_slot = 0;           //     and slot (the replay half must match them)
   uint64_t algo_static = 0;  // sum of list spans + k*12 over the uploaded queries
+  // disjunctive (OR) queries: their table, items and event slots, allocated
+  // by the first upload that holds one (n_or == 0: no extra launch)
+  int n_or = 0;                  // OR queries with at least one resolved term and k > 0
+  uint32_t or_items = 0;
+  int or_nt_max = 0;             // the most resolved terms of one of them
+  bool or_narrow = false, or_wide = false;   // some k <= kMaxK / > kMaxK among them
+  bool has_or = false;           // the uploaded queries include an OR query (even an empty one)
+  OrQuery* d_orq = nullptr;
+  size_t orq_cap = 0;            // entries
+  OrItem* d_oritem = nullptr;
+  uint32_t* d_orevcnt = nullptr;
+  size_t oritem_cap = 0;         // entries of both
+  Event* d_orev = nullptr;
+  uint64_t orev_cap = 0;
+  unsigned long long* d_orstat = nullptr;   // kNumOrStats counters of the last run
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // [4]: lean kernel end
   // Each batch runs on its own streams, so consecutive batches overlap on the
   // device (one's plan and first items under the other's last items); the
@@ -505,6 +520,8 @@ int copy_out(const std::string& s, char* out, int32_t cap, int32_t* len) {
 int check_snippet_query(const VacuumIndex& idx, const DocStore& docs, const wsr_query* q) {
   if (q->n_terms < 1 || q->n_terms > WSR_MAX_QUERY_TERMS) return fail(WSR_E_LIMIT, "bad term count");
   if (q->n_terms > WSR_MAX_TERMS && !q->more_ids) return fail(WSR_E_INVALID, "more_ids missing");
+  // (the highlighter takes a bag of every term in the doc)
+  if (q->flags & WSR_QUERY_OR) return fail(WSR_E_INVALID, "no snippets for a disjunctive query");
   if (!docs.is_open()) return fail(WSR_E_INVALID, "the index has no doc store (my.fdx / my.fdt)");
   for (int32_t id : query_terms(*q))
     if (id < 0 || id >= idx.n_lists())
@@ -707,7 +724,10 @@ void wsr_batch_destroy(wsr_handle* h, wsr_batch* b) {
                   static_cast<void*>(b->d_nhits), static_cast<void*>(b->d_stats),
                   static_cast<void*>(b->d_qdone), static_cast<void*>(b->d_itemq),
                   static_cast<void*>(b->d_pub), static_cast<void*>(b->d_ph),
-                  static_cast<void*>(b->d_xsend), static_cast<void*>(b->d_xrecv)})
+                  static_cast<void*>(b->d_xsend), static_cast<void*>(b->d_xrecv),
+                  static_cast<void*>(b->d_orq), static_cast<void*>(b->d_oritem),
+                  static_cast<void*>(b->d_orevcnt), static_cast<void*>(b->d_orev),
+                  static_cast<void*>(b->d_orstat)})
     if (p) (void)hipFree(p);
   if (b->h_ctr) (void)hipHostFree(b->h_ctr);
   for (auto& e : b->ev) if (e) (void)hipEventDestroy(e);
@@ -725,19 +745,92 @@ int wsr_check_query(wsr_handle* h, const wsr_query* q) {
   if (!h || !q) return fail(WSR_E_INVALID, "null argument");
   if (q->n_terms > WSR_MAX_QUERY_TERMS || q->k > WSR_MAX_K)
     return fail(WSR_E_LIMIT, "n_terms or k over the limit");
+  if (q->flags & ~(WSR_QUERY_PHRASE | WSR_QUERY_OR)) return fail(WSR_E_INVALID, "unknown flags");
+  if ((q->flags & WSR_QUERY_OR) && (q->flags & WSR_QUERY_PHRASE))
+    return fail(WSR_E_INVALID, "a query is a phrase or a disjunction, not both");
+  if ((q->flags & WSR_QUERY_OR) && q->n_terms > WSR_MAX_OR_TERMS)
+    return fail(WSR_E_LIMIT, "a disjunctive query has at most WSR_MAX_OR_TERMS terms");
   if (q->n_terms > WSR_MAX_TERMS && !q->more_ids)
     return fail(WSR_E_INVALID, "a query of more than WSR_MAX_TERMS terms needs more_ids");
   if ((q->flags & WSR_QUERY_PHRASE) && q->n_terms > WSR_MAX_PHRASE_TERMS)
     return fail(WSR_E_LIMIT, "a phrase query has at most WSR_MAX_PHRASE_TERMS terms");
-  if (q->flags & ~WSR_QUERY_PHRASE) return fail(WSR_E_INVALID, "unknown flags");
   if ((q->flags & WSR_QUERY_PHRASE) && q->n_terms > 1 && !h->positions)
     return fail(WSR_E_INVALID, "phrase query on an engine opened without positions");
   return WSR_OK;
 }
 
+// The plan of one disjunctive query (its resolved terms in oq->list): the
+// image's doc range cut into items at the last doc of every s-th block of the
+// query's longest list, s chosen so that an item carries about `target` blocks
+// over all its lists (doc ids spread alike over the lists' blocks), and each
+// item's event slot sized for its worst case -- every doc of its range an
+// event, or every posting of the blocks that overlap it.  Appends the items
+// and advances *ev_total.
+static void plan_or_query(const wsr_handle* h, uint32_t target, OrQuery* oq, std::vector<OrItem>* items,
+                          uint64_t* ev_total) {
+  const int nt = oq->nt;
+  // MaxScore bounds, summed in ascending (bound, slot) order
+  int by[kMaxOrTerms];
+  for (int t = 0; t < nt; ++t) by[t] = t;
+  auto ub = [&](int t) { return 2.2 * h->lists[oq->list[t]].idf; };
+  std::stable_sort(by, by + nt, [&](int a, int c) { return ub(a) < ub(c); });
+  double sum = 0.0;
+  for (int r = 0; r < nt; ++r) {
+    sum += ub(by[r]);
+    oq->ubsum[by[r]] = sum;
+  }
+  uint64_t total = 0;
+  int lg = 0;
+  uint32_t top = 0;   // one past the last doc of its lists in the image
+  for (int t = 0; t < nt; ++t) {
+    const ListDev& L = h->lists[oq->list[t]];
+    total += L.nblk;
+    if (L.nblk > h->lists[oq->list[lg]].nblk) lg = t;
+    top = std::max(top, L.last + 1);
+  }
+  const ListDev& G = h->lists[oq->list[lg]];
+  const uint32_t step = static_cast<uint32_t>(std::max<uint64_t>(1, uint64_t{target} * G.nblk / total));
+  const uint32_t img_lo = h->args.doc_lo, img_hi = std::min(h->args.doc_hi, top);
+  auto last_of = [&](const ListDev& L, uint32_t j) { return h->blocks[L.blk0 + j].last; };
+  // first block of L whose last doc is >= x (nblk: none)
+  auto first_block = [&](const ListDev& L, uint32_t x) {
+    const BlockDev* b0 = h->blocks.data() + L.blk0;
+    return static_cast<uint32_t>(
+        std::lower_bound(b0, b0 + L.nblk, x, [](const BlockDev& e, uint32_t v) { return e.last < v; }) - b0);
+  };
+  oq->item_base = static_cast<uint32_t>(items->size());
+  for (uint32_t j0 = 0; j0 < G.nblk; j0 += step) {
+    const uint32_t j1 = std::min(j0 + step, G.nblk);
+    const uint32_t lo = std::max(img_lo, j0 ? last_of(G, j0 - 1) + 1 : 0u);
+    const uint32_t hi = j1 == G.nblk ? img_hi : std::min(img_hi, last_of(G, j1 - 1) + 1);
+    if (lo >= hi) continue;
+    uint64_t blocks = 0;
+    for (int t = 0; t < nt; ++t) {
+      const ListDev& L = h->lists[oq->list[t]];
+      const uint32_t f = first_block(L, lo);
+      if (f < L.nblk) blocks += std::min(first_block(L, hi - 1), L.nblk - 1) - f + 1;
+    }
+    if (!blocks) continue;
+    OrItem it{};
+    it.oq = 0;   // (set at upload: the query's place in the table)
+    it.doc_lo = lo;
+    it.doc_hi = hi;
+    it.ev_cap = static_cast<uint32_t>(std::min<uint64_t>(hi - lo, 128 * blocks));
+    it.ev_base = *ev_total;
+    *ev_total += it.ev_cap;
+    items->push_back(it);
+  }
+  oq->n_items = static_cast<uint32_t>(items->size()) - oq->item_base;
+}
+
 int wsr_batch_upload(wsr_handle* h, wsr_batch* b, const wsr_query* q, int32_t nq) {
   if (!h || !b || (nq > 0 && !q) || nq < 0 || nq > b->max_q)
     return fail(WSR_E_INVALID, "bad upload arguments");
+  std::vector<OrQuery> orq;       // the disjunctive queries' table, items and event total
+  std::vector<OrItem> or_items;
+  uint64_t or_ev = 0;
+  bool has_or = false, or_narrow = false, or_wide = false;
+  int or_nt_max = 0;
   // (no handle lock: the handle's image is read-only after wsr_open and the
   // batch belongs to the caller, so threads with their own batches pipeline)
   std::vector<QueryIn> in(nq);
@@ -755,6 +848,41 @@ int wsr_batch_upload(wsr_handle* h, wsr_batch* b, const wsr_query* q, int32_t nq
       return fail(WSR_E_LIMIT, "query " + std::to_string(i) + ": k over the batch's hit stride");
     const int qrc = wsr_check_query(h, &s);
     if (qrc) return fail(qrc, "query " + std::to_string(i) + ": " + g_err);
+    if (s.flags & WSR_QUERY_OR) {
+      // a disjunctive query: an empty one to the conjunctive plan and kernels
+      // (neutral to the batch's class flags), planned here into its own table
+      QueryIn& d = in[i];
+      d.n_terms = 0;
+      d.k = s.k < 0 ? 0 : s.k;
+      d.flags = 0;
+      d.ext = 0;
+      for (int t = 0; t < kMaxTerms; ++t) d.list[t] = -1;
+      has_or = true;
+      // (only -1 means a missing term; n_terms <= WSR_MAX_OR_TERMS: the ids are inline)
+      for (int t = 0; t < s.n_terms; ++t)
+        if (s.list_ids[t] < -1 || s.list_ids[t] >= static_cast<int32_t>(h->lists.size()))
+          return fail(WSR_E_INVALID, "query " + std::to_string(i) + ": list id out of range");
+      if (s.k <= 0) continue;
+      OrQuery oq{};
+      oq.q = i;
+      oq.k = s.k;
+      for (int t = 0; t < s.n_terms; ++t) {
+        const int32_t id = s.list_ids[t];
+        if (id >= 0 && h->lists[id].nblk > 0) oq.list[oq.nt++] = id;   // (no blocks: none in this image)
+      }
+      if (oq.nt == 0) continue;
+      plan_or_query(h, b->seg_cap, &oq, &or_items, &or_ev);
+      for (int t = 0; t < oq.nt; ++t) algo += h->list_bytes[oq.list[t]];
+      algo += 12ull * oq.k;
+      for (uint32_t r = 0; r < oq.n_items; ++r)
+        or_items[oq.item_base + r].oq = static_cast<uint32_t>(orq.size());
+      if (oq.n_items) {
+        or_nt_max = std::max(or_nt_max, oq.nt);
+        (oq.k > kMaxK ? or_wide : or_narrow) = true;
+        orq.push_back(oq);
+      }
+      continue;
+    }
     const bool phrase = (s.flags & WSR_QUERY_PHRASE) && s.n_terms > 1;
     has_phrase = has_phrase || phrase;
     has_wide = has_wide || s.k > kMaxK;
@@ -837,6 +965,37 @@ int wsr_batch_upload(wsr_handle* h, wsr_batch* b, const wsr_query* q, int32_t nq
       b->q_cap = q_bytes + q_bytes / 4;
       HIP_OK(hipMalloc(&b->d_q, b->q_cap));
     }
+    if (!orq.empty()) {   // (a batch without a disjunctive query allocates nothing here)
+      if (or_items.size() > 0xFFFFFFFFull) return fail(WSR_E_LIMIT, "over 2^32 disjunctive work items");
+      if (orq.size() > b->orq_cap) {
+        if (b->d_orq) HIP_OK(hipFree(b->d_orq));
+        b->d_orq = nullptr;
+        b->orq_cap = 0;
+        HIP_OK(hipMalloc(&b->d_orq, sizeof(OrQuery) * (orq.size() + orq.size() / 4)));
+        b->orq_cap = orq.size() + orq.size() / 4;
+      }
+      if (or_items.size() > b->oritem_cap) {
+        if (b->d_oritem) HIP_OK(hipFree(b->d_oritem));
+        if (b->d_orevcnt) HIP_OK(hipFree(b->d_orevcnt));
+        b->d_oritem = nullptr;
+        b->d_orevcnt = nullptr;
+        b->oritem_cap = 0;
+        const size_t cap = or_items.size() + or_items.size() / 4 + 64;
+        HIP_OK(hipMalloc(&b->d_oritem, sizeof(OrItem) * cap));
+        HIP_OK(hipMalloc(&b->d_orevcnt, sizeof(uint32_t) * cap));
+        b->oritem_cap = cap;
+      }
+      if (or_ev > b->orev_cap) {
+        if (b->d_orev) HIP_OK(hipFree(b->d_orev));
+        b->d_orev = nullptr;
+        b->orev_cap = 0;
+        HIP_OK(hipMalloc(&b->d_orev, sizeof(Event) * (or_ev + or_ev / 4)));
+        b->orev_cap = or_ev + or_ev / 4;
+      }
+      if (!b->d_orstat) HIP_OK(hipMalloc(&b->d_orstat, sizeof(unsigned long long) * kNumOrStats));
+      HIP_OK(hipMemcpy(b->d_orq, orq.data(), sizeof(OrQuery) * orq.size(), hipMemcpyHostToDevice));
+      HIP_OK(hipMemcpy(b->d_oritem, or_items.data(), sizeof(OrItem) * or_items.size(), hipMemcpyHostToDevice));
+    }
     if (nq) HIP_OK(hipMemcpy(b->d_q, in.data(), sizeof(QueryIn) * nq, hipMemcpyHostToDevice));
     if (!ext.empty())
       HIP_OK(hipMemcpy(reinterpret_cast<char*>(b->d_q) + sizeof(QueryIn) * nq, ext.data(),
@@ -861,6 +1020,12 @@ int wsr_batch_upload(wsr_handle* h, wsr_batch* b, const wsr_query* q, int32_t nq
   b->lean_wgs_ph = static_cast<int>(std::max<uint64_t>(
       1, std::min<uint64_t>(h->lean_wgs_ph, (lean_need_ph + kLeanWaves - 1) / kLeanWaves)));
   b->algo_static = algo;
+  b->has_or = has_or;
+  b->n_or = static_cast<int>(orq.size());
+  b->or_items = static_cast<uint32_t>(or_items.size());
+  b->or_nt_max = or_nt_max;
+  b->or_narrow = or_narrow;
+  b->or_wide = or_wide;
   b->ran = false;
   return WSR_OK;
 }
@@ -899,6 +1064,7 @@ int wsr_debug_fail_runs(int32_t n) {
 
 static int batch_run(wsr_handle* h, wsr_batch* b, const ShardEmit* se, const OwnerJob* oj) {
   if (!h || !b) return fail(WSR_E_INVALID, "null argument");
+  if (se && b->has_or) return fail(WSR_E_INVALID, "a doc-range shard step cannot run a disjunctive query");
   for (int32_t f = g_fail_runs.load(); f > 0;)
     if (g_fail_runs.compare_exchange_weak(f, f - 1)) return fail(WSR_E_HIP, "injected run failure");
   wsr_batch* pb = nullptr;   // (a host replay taken, below)
@@ -1004,6 +1170,14 @@ static int batch_run(wsr_handle* h, wsr_batch* b, const ShardEmit* se, const Own
     if (!se && b->has_wide)
       HIP_OK(launch_wide_replay(b->d_q, b->d_plan, b->nq, b->d_events, b->d_evcnt, b->d_hits, b->stride,
                                 b->d_nhits, st));
+    if (b->n_or) {
+      // the disjunctive queries, after the plan's writes of their (empty) rows
+      HIP_OK(hipMemsetAsync(b->d_orstat, 0, sizeof(unsigned long long) * kNumOrStats, st));
+      HIP_OK(launch_or_items(h->args, b->d_orq, b->d_oritem, b->or_items, b->or_nt_max, b->d_orev, b->d_orevcnt,
+                             b->d_ctr, b->d_orstat, st));
+      HIP_OK(launch_or_replay(b->d_orq, static_cast<uint32_t>(b->n_or), b->d_oritem, b->d_orev, b->d_orevcnt,
+                              b->d_hits, b->stride, b->d_nhits, b->or_narrow, b->or_wide, st));
+    }
     HIP_OK(hipEventRecord(b->ev[3], st));
   } catch (const std::exception& e) {
     if (pb) {
@@ -1164,6 +1338,27 @@ int wsr_batch_stats_get(wsr_handle* h, wsr_batch* b, wsr_batch_stats* out) {
   return WSR_OK;
 }
 
+int wsr_batch_or_stats_get(wsr_handle* h, wsr_batch* b, wsr_or_stats* out) {
+  if (!h || !b || !out || !b->ran) return fail(WSR_E_INVALID, "batch has not been run");
+  *out = wsr_or_stats{};
+  if (!b->n_or) return WSR_OK;
+  std::lock_guard<std::mutex> g(h->mu);
+  try {
+    HIP_OK(hipSetDevice(h->device));
+    HIP_OK(hipStreamSynchronize(b->st));
+    unsigned long long v[kNumOrStats];
+    HIP_OK(hipMemcpy(v, b->d_orstat, sizeof v, hipMemcpyDeviceToHost));
+    out->items = v[kOrStatItems];
+    out->windows = v[kOrStatWindows];
+    out->windows_skipped = v[kOrStatSkipped];
+    out->touched_docs = v[kOrStatTouched];
+    out->events = v[kOrStatEvents];
+  } catch (const std::exception& e) {
+    return fail(WSR_E_HIP, e.what());
+  }
+  return WSR_OK;
+}
+
 int wsr_search_batch(wsr_handle* h, const wsr_query* q, int32_t nq, int32_t stride, wsr_hit* hits,
                      int32_t* n_hits) {
   if (!h || nq < 0 || (nq && (!q || !hits || !n_hits))) return fail(WSR_E_INVALID, "bad arguments");
@@ -1284,13 +1479,19 @@ int wsr_search_text(wsr_handle* h, const char* text, int64_t len, int32_t k, int
 int wsr_class_order(const wsr_query* q, int32_t nq, int32_t* order, int32_t* n_conj) {
   if (nq < 0 || (nq && (!q || !order)) || !n_conj) return fail(WSR_E_INVALID, "bad class_order arguments");
   // (a one-term phrase is a single-term query: the same class as in the plan)
-  auto phrase = [&](int32_t i) { return (q[i].flags & WSR_QUERY_PHRASE) != 0 && q[i].n_terms > 1; };
+  // (a disjunctive query runs in kernels of its own: the last class)
+  auto disj = [&](int32_t i) { return (q[i].flags & WSR_QUERY_OR) != 0; };
+  auto phrase = [&](int32_t i) {
+    return !disj(i) && (q[i].flags & WSR_QUERY_PHRASE) != 0 && q[i].n_terms > 1;
+  };
   int32_t n = 0;
   for (int32_t i = 0; i < nq; ++i)
-    if (!phrase(i)) order[n++] = i;
+    if (!phrase(i) && !disj(i)) order[n++] = i;
   *n_conj = n;
   for (int32_t i = 0; i < nq; ++i)
     if (phrase(i)) order[n++] = i;
+  for (int32_t i = 0; i < nq; ++i)
+    if (disj(i)) order[n++] = i;
   return WSR_OK;
 }
 
@@ -1697,6 +1898,7 @@ static uint64_t region_events_of(int32_t q_per_owner, int64_t slot) {
 static int check_step(wsr_handle* h, wsr_batch* b, int W, int32_t q_per_owner, int64_t slot) {
   if (!h || !b || W < 1 || q_per_owner <= 0 || slot <= 0 || static_cast<int64_t>(q_per_owner) * W != b->nq)
     return fail(WSR_E_INVALID, "bad shard_step arguments (the batch must hold world * q_per_owner queries)");
+  if (b->has_or) return fail(WSR_E_INVALID, "a doc-range shard step cannot run a disjunctive query");
   if (W > kMaxOwners) return fail(WSR_E_LIMIT, "more than kMaxOwners ranks");
   if (static_cast<uint64_t>(slot) > 0xFFFFFFFFull) return fail(WSR_E_LIMIT, "slot over 2^32 events");
   return WSR_OK;
@@ -2058,6 +2260,7 @@ int wsr_shard_step_replay(wsr_handle* h, wsr_batch* b, int32_t rank, int32_t wor
       !b->x_fused || b->x_world != world || b->x_qpr != q_per_owner || b->x_slot != slot ||
       static_cast<int64_t>(q_per_owner) * world != b->nq)
     return fail(WSR_E_INVALID, "call wsr_shard_step_emit with the same world, q_per_owner and slot first");
+  if (b->has_or) return fail(WSR_E_INVALID, "a doc-range shard step cannot run a disjunctive query");
   try {
     HIP_OK(hipSetDevice(h->device));
     HIP_OK(hipMemcpyAsync(b->d_xrecv, host_recv, sizeof(Event) * region_events_of(q_per_owner, slot) * world,
@@ -2078,6 +2281,7 @@ int wsr_shard_step_replay_deferred(wsr_handle* h, wsr_batch* b, int32_t rank, in
       !b->x_fused || b->x_world != world || b->x_qpr != q_per_owner || b->x_slot != slot ||
       static_cast<int64_t>(q_per_owner) * world != b->nq)
     return fail(WSR_E_INVALID, "call wsr_shard_step_emit with the same world, q_per_owner and slot first");
+  if (b->has_or) return fail(WSR_E_INVALID, "a doc-range shard step cannot run a disjunctive query");
   if (b->has_wide)   // (the LDS heap: the replay launch of its own)
     return wsr_shard_step_replay(h, b, rank, world, q_per_owner, slot, host_recv);
   try {

@@ -184,6 +184,36 @@ struct QueryDesc {
 static_assert(sizeof(QueryDesc) == 128, "QueryDesc layout");
 constexpr uint32_t kNoSlot = 0xFFFFu;
 
+// Disjunctive (OR) queries (wsr_query.flags & WSR_QUERY_OR) live in a table of
+// their own: the QueryIn the conjunctive plan and kernels see shows them as
+// empty queries.  The host resolves the terms (missing ones dropped), cuts the
+// image's doc range into work items of about IndexArgs::seg_cap blocks over
+// all of the query's lists, and sizes each item's event slot for its worst case.
+constexpr int32_t kQueryOr = 2;
+constexpr int kMaxOrTerms = 16;           // terms of an OR query (the ids held inline)
+constexpr uint32_t kOrWindow = 2048;      // docs of or_kernel's accumulator window (a power of two)
+struct OrQuery {
+  int32_t q;            // the query's index in the batch (its hits row)
+  int32_t k;            // n_results (> 0)
+  int32_t nt;           // resolved terms (> 0)
+  uint32_t item_base;   // first of its items in the OrItem table
+  uint32_t n_items;
+  uint32_t pad;
+  int32_t list[kMaxOrTerms];    // list ids of the resolved terms, in query order
+  double ubsum[kMaxOrTerms];    // MaxScore: the sum of the score bounds (2.2 * idf) of term t and
+                                // of every term that sorts before it by (bound, slot)
+};
+static_assert(sizeof(OrQuery) == 216, "OrQuery layout");
+struct OrItem {
+  uint32_t oq;          // its query's entry in the OrQuery table
+  uint32_t doc_lo, doc_hi;   // the item's docs: [doc_lo, doc_hi)
+  uint32_t ev_cap;      // events its slot holds
+  uint64_t ev_base;     // first event of its slot
+};
+static_assert(sizeof(OrItem) == 24, "OrItem layout");
+// or_kernel's counters (wsr_or_stats), one u64 each
+enum { kOrStatItems = 0, kOrStatWindows, kOrStatSkipped, kOrStatTouched, kOrStatEvents, kNumOrStats };
+
 // A heap-insertion event: a survivor that a top-k heap run from empty over its
 // segment inserts (query_processing.h:595-602).
 struct Event {

@@ -203,4 +203,19 @@ hipError_t launch_owner_replay_meta(const QueryIn* q, int q0, int nq, int n_shar
 // resident 64-thread segment workgroups per CU
 int segment_kernel_occupancy();
 
+// Disjunctive (OR) queries: one wave per item accumulates every term's BM25
+// into an LDS window of kOrWindow docs, term by term in query order, and
+// emits the touched docs in doc order through the item's running top-k
+// (every touched doc for k > kMaxK); ev_cnt[i] = events of item i; stats:
+// kNumOrStats u64 (zeroed by the caller).  nt_max: the most resolved terms of
+// a query of the table (sizes the decoded-block cache in LDS).
+hipError_t launch_or_items(const IndexArgs& ix, const OrQuery* oq, const OrItem* items, uint32_t n_items,
+                           int nt_max, Event* events, uint32_t* ev_cnt, uint32_t* counters,
+                           unsigned long long* stats, hipStream_t st);
+// one wave per OR query: its items' events, in doc order, through the
+// restated heap (narrow: k <= kMaxK in the wave's lanes; wide: in LDS)
+hipError_t launch_or_replay(const OrQuery* oq, uint32_t n_or, const OrItem* items, const Event* events,
+                            const uint32_t* ev_cnt, HitDev* hits, int hit_stride, int32_t* n_hits,
+                            bool narrow, bool wide, hipStream_t st);
+
 }  // namespace wiser

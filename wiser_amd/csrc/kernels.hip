@@ -3405,7 +3405,302 @@ __device__ __noinline__ void owner_replay_tail(const QueryIn* qs, const int32_t*
     owner_replay_query<false>(qs, static_cast<int>(qi), b0, ns, meta, ms, st, recv, hits, hs, n_hits, counters);
 }
 
+// ------------------------------------------------------- disjunctive (OR) --
+// One wave per item (a doc-id range of the image, cut by the host).  The
+// range is walked in windows of kOrWindow docs, aligned to kOrWindow: an f64
+// accumulator per doc and a touched bitmap in LDS.  Per window the terms are
+// handled one after the other, in query order: the blocks of the term's list
+// that overlap the window are decoded (each list's current block stays
+// decoded in LDS, so a block that spans several windows is decoded once), and
+// every posting inside the window adds bm25_term(idf, tf, norm[plen]) to its
+// doc's accumulator.  Doc ids are unique within a list, so the adds of one
+// term never meet; a wave barrier between terms fixes the order of the
+// additions to the query's term order, and the first add is 0.0 + x (exact):
+// a doc's sum is the reference's left-to-right f64 sum over the terms it holds.
+// The touched docs then pass, in doc order, through the item's running top-k
+// (EventFilter; every touched doc for k > kMaxK) into the item's event slot.
+//
+// MaxScore (k <= kMaxK): a term's score is below 2.2 * idf.  Once the running
+// top-k is full, the terms whose bounds -- summed in ascending order -- stay at
+// or below 0.998 times its k-th best are non-essential: a doc that holds only
+// such terms scores at most that sum, which is below the k-th best of the
+// item's own docs so far and so not above the reference heap's minimum at
+// that doc (the heap has seen those docs and more): it is never an insertion,
+// and the filter would drop it unchanged.  Non-essential terms therefore stop
+// starting windows -- the next window is the one of the smallest unconsumed
+// doc id over the essential lists -- and are still accumulated inside the
+// windows the others start.
+struct OrLds {
+  double acc[kOrWindow];
+  uint32_t bits[kOrWindow / 32];
+  double norm[256];
+  Event evs[64];
+  uint32_t cur[kMaxOrTerms];      // per term slot: first block of its list not wholly consumed
+  uint32_t cached[kMaxOrTerms];   // ... the block decoded in its cache row (kNoBlock: none)
+};
+static_assert(kOrWindow == 2048, "or_kernel: one bitmap word per lane");
+constexpr double kOrMargin = 0.998;   // the pre-probe pruning's margin
+
+__global__ __launch_bounds__(64) void or_kernel(IndexArgs ix, const OrQuery* __restrict__ oqs,
+                                                const OrItem* __restrict__ items, uint32_t n_items,
+                                                Event* __restrict__ events, uint32_t* __restrict__ ev_cnt,
+                                                uint32_t* __restrict__ counters,
+                                                unsigned long long* __restrict__ stats) {
+  __shared__ OrLds S;
+  // per term slot the current block of its list, decoded: 128 doc ids, 128 tfs
+  extern __shared__ uint32_t or_cache[];
+  const uint32_t l = threadIdx.x & 63;
+  const uint32_t it = blockIdx.x;
+  if (it >= n_items) return;
+  const OrItem I = items[it];
+  const OrQuery* Q = oqs + I.oq;
+  const uint32_t nt = uni(static_cast<uint32_t>(Q->nt));
+  const uint32_t k = uni(static_cast<uint32_t>(Q->k));
+  const bool wide = k > static_cast<uint32_t>(kMaxK);   // every touched doc is an event
+  const uint32_t dhi = uni(I.doc_hi), ev_cap = uni(I.ev_cap);
+  Event* ev_out = events + I.ev_base;
+#pragma unroll
+  for (uint32_t i = 0; i < 4; ++i) S.norm[l + 64 * i] = ix.cache[l + 64 * i];
+  for (uint32_t i = l; i < kOrWindow; i += 64) S.acc[i] = 0.0;
+  S.bits[l] = 0u;
+  if (l < static_cast<uint32_t>(kMaxOrTerms)) {
+    S.cur[l] = 0u;
+    S.cached[l] = kNoBlock;
+  }
+  const double ubsum = l < nt ? Q->ubsum[l] : 0.0;
+  const uint32_t all = (1u << nt) - 1u;
+  uint32_t ess = all;   // essential term slots
+  __builtin_amdgcn_wave_barrier();
+
+  // block c of list L decoded in slot t's cache row; its posting count
+  auto load_block = [&](uint32_t t, const ListDev& L, uint32_t c) __attribute__((always_inline)) {
+    const uint32_t cnt = c == L.nblk - 1 ? L.tail_cnt : 128u;
+    if (uni(S.cached[t]) == c) return cnt;
+    uint32_t* d = or_cache + t * 256u;
+    __builtin_amdgcn_wave_barrier();
+    if (c == L.nblk - 1 && L.tail != kNoTail) {   // a VInts last block, decoded at load
+      const uint32_t* tp = ix.tails + L.tail;
+      d[l] = l < cnt ? tp[l] : 0u;
+      d[l + 64] = l + 64 < cnt ? tp[l + 64] : 0u;
+      d[128 + l] = l < cnt ? tp[cnt + l] : 0u;
+      d[192 + l] = l + 64 < cnt ? tp[cnt + l + 64] : 0u;
+    } else {
+      const BlockDev bd = ix.blocks[L.blk0 + c];
+      const uint32_t m = uni(ix.blk_meta[L.blk0 + c]);
+      decode_block<true>(ix.blob + L.base + uni(bd.doc_rel), m & 0xFF, cnt, true, uni(bd.prev), d);
+      decode_block<true>(ix.blob + L.base + uni(bd.tf_rel), m >> 8, cnt, false, 0u, d + 128);
+    }
+    if (l == 0) S.cached[t] = c;
+    __builtin_amdgcn_wave_barrier();
+    return cnt;
+  };
+  // slot t's cursor moved to the first block with a doc >= x
+  auto advance = [&](uint32_t t, const ListDev& L, uint32_t x) __attribute__((always_inline)) {
+    const uint32_t c = uni(find_block(ix.blk_last + L.blk0, uni(S.cur[t]), L.nblk, x));
+    __builtin_amdgcn_wave_barrier();
+    if (l == 0) S.cur[t] = c;
+    __builtin_amdgcn_wave_barrier();
+    return c;
+  };
+
+  EventFilter F;
+  F.k = k;
+  uint32_t ev_n = 0, evb = 0;
+  bool over = false;
+  uint32_t n_win = 0, n_skip = 0, n_touch = 0;
+  auto flush = [&]() __attribute__((always_inline)) {
+    __builtin_amdgcn_wave_barrier();
+    if (ev_n <= ev_cap) {
+      if (l < evb) ev_out[ev_n - evb + l] = S.evs[l];
+    } else {
+      over = true;
+    }
+    __builtin_amdgcn_wave_barrier();
+    evb = 0;
+  };
+  auto emit = [&](double sv, int32_t dv) __attribute__((always_inline)) {
+    if (evb == 64u) flush();
+    if (l == 0) {
+      Event e;
+      e.score = sv;
+      e.doc = dv;
+      e.pad = 0;
+      S.evs[evb] = e;
+    }
+    ++ev_n;
+    ++evb;
+  };
+
+  uint32_t pos = uni(I.doc_lo);   // docs below pos are consumed
+  while (pos < dhi) {
+    // the smallest unconsumed doc id over the essential lists
+    uint32_t next = dhi;
+    uint32_t ne_end = 0;   // (statistics) one past the last doc of the non-essential lists still open
+    for (uint32_t t = 0; t < nt; ++t) {
+      const ListDev L = ix.lists[Q->list[t]];
+      const uint32_t c = advance(t, L, pos);
+      if (c >= L.nblk) continue;
+      if (!((ess >> t) & 1u)) {
+        ne_end = umax(ne_end, L.last + 1u);
+        continue;
+      }
+      if (uni(ix.blocks[L.blk0 + c].prev) >= next) continue;   // its docs lie past `next`
+      const uint32_t cnt = load_block(t, L, c);
+      const uint32_t* d = or_cache + t * 256u;
+      // (the block's last doc is >= pos: the count of docs below pos is < cnt)
+      const uint32_t below = __popcll(__ballot(l < cnt && d[l] < pos)) +
+                             __popcll(__ballot(l + 64 < cnt && d[l + 64] < pos));
+      const uint32_t first = uni(d[below < cnt ? below : cnt - 1]);
+      next = first < next ? first : next;
+    }
+    next = umax(next, pos);   // (every window ends past pos)
+    const uint32_t wb = next & ~(kOrWindow - 1u);
+    const uint32_t lo = umax(wb, pos);
+    {
+      // windows jumped over while a non-essential list still had postings
+      const uint32_t to = next >= dhi ? dhi : lo;
+      const uint32_t end = to < ne_end ? to : ne_end;
+      if (end > pos) n_skip += (end - pos + kOrWindow - 1u) / kOrWindow;
+    }
+    if (next >= dhi) break;
+    const uint32_t hi = dhi - wb > kOrWindow ? wb + kOrWindow : dhi;
+    ++n_win;
+    for (uint32_t t = 0; t < nt; ++t) {
+      const ListDev L = ix.lists[Q->list[t]];
+      uint32_t c = advance(t, L, lo);
+      const double idf = L.idf;
+      while (c < L.nblk) {
+        if (uni(ix.blocks[L.blk0 + c].prev) >= hi) break;   // the block starts past the window
+        const uint32_t cnt = load_block(t, L, c);
+        const uint32_t* d = or_cache + t * 256u;
+        const uint8_t* pl = ix.plen + static_cast<uint64_t>(L.blk0 + c) * 128u;
+#pragma unroll
+        for (uint32_t j = l; j < 128u; j += 64u) {
+          const uint32_t doc = d[j];
+          if (j < cnt && doc >= lo && doc < hi) {
+            const uint32_t i = doc - wb;
+            S.acc[i] = S.acc[i] + bm25_term(idf, d[128 + j], S.norm[pl[j]]);
+            atomicOr(&S.bits[i >> 5], 1u << (i & 31u));
+          }
+        }
+        if (uni(ix.blk_last[L.blk0 + c]) >= hi) break;   // it goes on in the next window
+        ++c;
+      }
+      __builtin_amdgcn_wave_barrier();
+      if (l == 0) S.cur[t] = c;
+      __builtin_amdgcn_wave_barrier();   // (and the next term's adds come after this term's)
+    }
+    // the touched docs, in doc order: chunk ch = docs wb + 64 * ch + lane
+    const uint32_t w = S.bits[l];
+    uint64_t nz = __ballot(w != 0u);
+    while (nz) {
+      const uint32_t ch = static_cast<uint32_t>(__builtin_ctzll(nz)) >> 1;
+      nz &= ~(3ull << (2u * ch));
+      // (readlane returns an int: through uint32_t, or the low word's bit 31 would sign-extend)
+      const uint32_t m_lo = static_cast<uint32_t>(__builtin_amdgcn_readlane(w, static_cast<int>(2u * ch)));
+      const uint32_t m_hi = static_cast<uint32_t>(__builtin_amdgcn_readlane(w, static_cast<int>(2u * ch + 1u)));
+      const uint64_t m = (static_cast<uint64_t>(m_hi) << 32) | m_lo;
+      const bool touched = (m >> l) & 1ull;
+      const uint32_t i = 64u * ch + l;
+      const double sc = S.acc[i];
+      const int32_t doc = static_cast<int32_t>(wb + i);
+      const uint32_t n = __popcll(m);
+      n_touch += n;
+      if (wide) {
+        if (ev_n + n <= ev_cap) {
+          if (touched) {
+            Event e;
+            e.score = sc;
+            e.doc = doc;
+            e.pad = 0;
+            ev_out[ev_n + __popcll(m & lanemask_lt())] = e;
+          }
+        } else {
+          over = true;
+        }
+        ev_n += n;
+      } else {
+        F.step(sc, doc, touched, emit);
+      }
+      if (touched) S.acc[i] = 0.0;
+    }
+    S.bits[l] = 0u;
+    __builtin_amdgcn_wave_barrier();
+    pos = hi;
+    if (!wide && F.pt_n >= k) {
+      const double thr = readlane_f64(F.pt, static_cast<int>(k) - 1) * kOrMargin;
+      ess = static_cast<uint32_t>(__ballot(l < nt && !(ubsum <= thr)));
+    }
+  }
+  if (evb) flush();
+  if (l == 0) {
+    ev_cnt[it] = over ? 0u : ev_n;
+    if (over) atomicOr(&counters[kCtrError], static_cast<uint32_t>(kErrCapacity));
+    atomicAdd(&stats[kOrStatItems], 1ull);
+    atomicAdd(&stats[kOrStatWindows], static_cast<unsigned long long>(n_win));
+    atomicAdd(&stats[kOrStatSkipped], static_cast<unsigned long long>(n_skip));
+    atomicAdd(&stats[kOrStatTouched], static_cast<unsigned long long>(n_touch));
+    atomicAdd(&stats[kOrStatEvents], static_cast<unsigned long long>(ev_n));
+  }
+}
+
+// One wave per OR query: the events of its items (doc-id order) through the
+// restated heap (HeapSink, or LdsHeapSink for k > kMaxK), then SortHeap.
+template <bool kWide>
+__global__ __launch_bounds__(64) void or_replay_kernel(const OrQuery* __restrict__ oqs, uint32_t n_or,
+                                                       const OrItem* __restrict__ items,
+                                                       const Event* __restrict__ events,
+                                                       const uint32_t* __restrict__ ev_cnt,
+                                                       HitDev* __restrict__ hits, int hit_stride,
+                                                       int32_t* __restrict__ n_hits) {
+  __shared__ double s_hs[kWide ? kMaxKWide : 1];
+  __shared__ int32_t s_hd[kWide ? kMaxKWide : 1];
+  if (blockIdx.x >= n_or) return;
+  const OrQuery* Q = oqs + blockIdx.x;
+  const uint32_t k = uni(static_cast<uint32_t>(Q->k));
+  if ((k > static_cast<uint32_t>(kMaxK)) != kWide) return;
+  const uint32_t base = uni(Q->item_base), n = uni(Q->n_items);
+  const int64_t qi = static_cast<int64_t>(uni(static_cast<uint32_t>(Q->q)));
+  auto count_of = [&](uint32_t r) { return ev_cnt[base + r]; };
+  auto base_of = [&](uint32_t r) { return events + items[base + r].ev_base; };
+  if constexpr (kWide) {
+    LdsHeapSink sink;
+    sink.hs = s_hs;
+    sink.hd = s_hd;
+    sink.k = k;
+    consume_stream<false>(sink, n, count_of, base_of, [](double, int32_t) {});
+    sink.finish(hits + qi * hit_stride, &n_hits[qi]);
+  } else {
+    HeapSink sink;
+    sink.k = k;
+    consume_stream<false>(sink, n, count_of, base_of, [](double, int32_t) {});
+    sink.finish(hits + qi * hit_stride, &n_hits[qi]);
+  }
+}
+
 // ------------------------------------------------------------ launchers --
+hipError_t launch_or_items(const IndexArgs& ix, const OrQuery* oq, const OrItem* items, uint32_t n_items,
+                           int nt_max, Event* events, uint32_t* ev_cnt, uint32_t* counters,
+                           unsigned long long* stats, hipStream_t st) {
+  if (!n_items) return hipSuccess;
+  hipLaunchKernelGGL(or_kernel, dim3(n_items), dim3(64), sizeof(uint32_t) * 256u * static_cast<uint32_t>(nt_max),
+                     st, ix, oq, items, n_items, events, ev_cnt, counters, stats);
+  return hipGetLastError();
+}
+
+hipError_t launch_or_replay(const OrQuery* oq, uint32_t n_or, const OrItem* items, const Event* events,
+                            const uint32_t* ev_cnt, HitDev* hits, int hit_stride, int32_t* n_hits,
+                            bool narrow, bool wide, hipStream_t st) {
+  if (!n_or) return hipSuccess;
+  if (narrow)
+    hipLaunchKernelGGL(or_replay_kernel<false>, dim3(n_or), dim3(64), 0, st, oq, n_or, items, events, ev_cnt,
+                       hits, hit_stride, n_hits);
+  if (wide)
+    hipLaunchKernelGGL(or_replay_kernel<true>, dim3(n_or), dim3(64), 0, st, oq, n_or, items, events, ev_cnt,
+                       hits, hit_stride, n_hits);
+  return hipGetLastError();
+}
+
 hipError_t launch_plan(const IndexArgs& ix, const QueryIn* q, int nq, QueryPlan* plan,
                        uint32_t* counters, uint64_t ev_capacity, uint32_t item_capacity,
                        int lean_grid, int lean_grid_ph, int seg_grid, const FusedReplay& fr, uint32_t* item_q,

@@ -18,6 +18,11 @@ Behaviour kept from the reference:
   * ``is_phrase`` with two or more terms ranks only docs holding the terms at
     consecutive positions (QueryProcessor, query_processing.h:854-912); the
     engine must be loaded with ``positions=True`` (the default).
+Beyond the reference: ``match_any`` makes a query disjunctive (WSR_QUERY_OR) --
+a doc matches when it holds at least one of the terms, a term missing from the
+dictionary contributes nothing (``doc_freqs`` has a 0 for it), and the score is
+the sum of the BM25 terms of the lists that hold the doc.  Not with
+``is_phrase`` or ``return_snippets`` (WSR_E_INVALID).
 Snippets (SearchQuery.return_snippets): a host stage after the GPU top-k, as
 in the reference (vacuum_engine.h:243-253): offsets from the index, text from the
 doc store (my.fdx / my.fdt), SimpleHighlighter -- wsr_snippet in the C ABI.
@@ -40,6 +45,7 @@ class SearchQuery:
     return_snippets: bool = False
     n_snippet_passages: int = 3
     is_phrase: bool = False
+    match_any: bool = False     # disjunctive (OR): rank the docs that hold any of the terms
 
 
 @dataclass
@@ -160,6 +166,8 @@ class VacuumEngine:
             raise NotImplementedError(f"more than {_capi.MAX_QUERY_TERMS} terms per query")
         if query.n_results > _capi.MAX_K:
             raise NotImplementedError(f"n_results above {_capi.MAX_K}")
+        if query.match_any and (query.is_phrase or query.return_snippets):
+            raise _capi.WiserError(_capi.E_INVALID, "match_any goes with neither is_phrase nor return_snippets")
         q = _capi.Query()
         q.k = max(0, int(query.n_results))
         q.flags = _capi.QUERY_PHRASE if (query.is_phrase and len(query.terms) > 1) else 0
@@ -169,6 +177,13 @@ class VacuumEngine:
             ids.append(lid)
             dfs.append(df)
         missing = any(i < 0 for i in ids) or not ids
+        if query.match_any:
+            # a missing term contributes nothing (its doc_freq is 0); the engine
+            # checks the term limit (WSR_MAX_OR_TERMS)
+            q.flags = _capi.QUERY_OR
+            missing = not ids
+            if len(ids) > _capi.MAX_OR_TERMS:   # (loud whatever k is: k = 0 never reaches the engine's check)
+                raise _capi.WiserError(_capi.E_LIMIT, f"more than {_capi.MAX_OR_TERMS} terms in a match_any query")
         q.n_terms = 0 if (missing or q.k == 0) else len(ids)
         for i, lid in enumerate(ids[:_capi.MAX_TERMS]):
             q.list_ids[i] = lid
@@ -258,11 +273,13 @@ class DocsHost:
         except Exception:
             pass
 
-    def query(self, terms: Sequence[str], is_phrase: bool = False):
+    def query(self, terms: Sequence[str], is_phrase: bool = False, match_any: bool = False):
         q = _capi.Query()
         q.n_terms = len(terms)
         q.k = 1
         q.flags = _capi.QUERY_PHRASE if (is_phrase and len(terms) > 1) else 0
+        if match_any:   # (a disjunctive query has no snippets: wsr_docs_snippet refuses it)
+            q.flags |= _capi.QUERY_OR
         for i, t in enumerate(terms):
             lid, df = C.c_int32(), C.c_int32()
             check(lib.wsr_docs_lookup(self._h, t.encode(), C.byref(lid), C.byref(df)))
@@ -326,6 +343,16 @@ class ResidentBatch:
         st = _capi.BatchStats()
         check(lib.wsr_batch_stats_get(self.engine._h, self._b, C.byref(st)))
         return st
+
+    def or_stats(self) -> _capi.OrStats:
+        """Counters of the last run's disjunctive queries (wsr_batch_or_stats_get)."""
+        st = _capi.OrStats()
+        check(lib.wsr_batch_or_stats_get(self.engine._h, self._b, C.byref(st)))
+        return st
+
+    def set_item_blocks(self, blocks: int) -> None:
+        """wsr_batch_set_item_blocks (disjunctive queries: before the upload)."""
+        check(lib.wsr_batch_set_item_blocks(self.engine._h, self._b, blocks))
 
     def close(self) -> None:
         if self._b is not None:
@@ -496,8 +523,9 @@ def gen_realistic_log(index_dir: str, out_path: str, n_queries: int = 20_000, ph
 
 def class_order(queries) -> Tuple[List[int], int]:
     """wsr_class_order: a stable order of `queries` (a ctypes array of
-    _capi.Query) with the conjunctive queries first and the phrase queries
-    after them -> (order, n_conj).  Batches cut from it are class-pure."""
+    _capi.Query) with the conjunctive queries first, the phrase queries after
+    them and the disjunctive ones last -> (order, n_conj).  Batches cut from it
+    are class-pure."""
     n = len(queries)
     order = (C.c_int32 * max(n, 1))()
     nc = C.c_int32()
@@ -508,11 +536,12 @@ def class_order(queries) -> Tuple[List[int], int]:
 def class_batches(queries, batch: int) -> List[List[int]]:
     """The engine's batch former for a query stream: indices of `queries`
     (ctypes Query array) in batches of at most `batch`, each class cut
-    separately (wsr_class_order), so no batch mixes phrase and conjunctive
-    queries."""
+    separately (wsr_class_order), so no batch mixes phrase, conjunctive and
+    disjunctive queries."""
     order, nc = class_order(queries)
+    n_or = sum(1 for q in queries if q.flags & _capi.QUERY_OR)
     out = []
-    for lo, hi in ((0, nc), (nc, len(order))):
+    for lo, hi in ((0, nc), (nc, len(order) - n_or), (len(order) - n_or, len(order))):
         for s in range(lo, hi, batch):
             out.append(order[s:min(s + batch, hi)])
     return out
