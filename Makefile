@@ -21,12 +21,20 @@ ORAFLAGS := -O3 -DNDEBUG -std=c++17 -fPIC -ffp-contract=off -Wall -shared
 CLI     := wiser_amd/_lib/engine_cli
 CALIB   := wiser_amd/_lib/calib_ea
 DICT    := wiser_amd/_lib/dict_check
+DEVMEM  := wiser_amd/_lib/dev_mem_check
 
-all: $(LIB) $(ORACLE) $(CLI) $(CALIB) $(DICT)
+# (the buffer owner's check is a test of the header alone: a tree whose tests/
+# does not hold its source still builds everything else)
+all: $(LIB) $(ORACLE) $(CLI) $(CALIB) $(DICT) $(if $(wildcard tests/cpp/dev_mem_check.cc),$(DEVMEM))
 
 # CPU check of the term dictionary (tests/test_dictionary.py)
 $(DICT): tests/cpp/dict_check.cc wiser_amd/csrc/index.h $(LIB)
 	$(CXX) -O2 -std=c++17 -I/opt/rocm/include -D__HIP_PLATFORM_AMD__ -o $@ tests/cpp/dict_check.cc -Lwiser_amd/_lib -lwiser_hip -Wl,-rpath,'$$ORIGIN'
+
+# CPU check of the buffer owner over a fake memory policy (tests/test_dev_mem.py): no HIP, no engine
+$(DEVMEM): tests/cpp/dev_mem_check.cc wiser_amd/csrc/dev_mem.h
+	@mkdir -p wiser_amd/_lib
+	$(CXX) -O2 -std=c++17 -Wall -o $@ tests/cpp/dev_mem_check.cc
 
 # counter calibration (profiles only): known-byte reads for rocprofv3 --pmc
 $(CALIB): scripts/calib_ea.hip

@@ -319,3 +319,66 @@ def test_many_terms(synth_small, mode):
     for i, q in enumerate(long_q + qs[:5]):
         assert [(hits[i * 10 + j].doc_id, hits[i * 10 + j].score) for j in range(nh[i])] == orc.search(q, 10)[0]
     eng.close()
+
+
+def test_batch_regrowth(synth_small):
+    """One resident batch through three uploads: a single rare-term query (every
+    on-demand buffer at its smallest), then a full batch that grows all of them
+    at once -- head-term single- and two-term queries (many driver blocks: the
+    event slots and the per-item arrays), conjunctive queries of 17 to 40 terms
+    (their term table follows the query array, which a full batch alone fills
+    to the byte: the query buffer grows), OR queries of head terms (their
+    table, items and event slots) and a k = 100 query -- then the first upload
+    again, which fits and so reallocates nothing: the larger buffers'
+    stale contents must not reach its result.  Every run bit for bit against
+    the oracle (the OR queries: against its per-term contributions, or_model)."""
+    from oracle.oracle import OracleVacuum
+    from or_model import OrModel
+    import wiser_amd as w
+    from wiser_amd import _capi
+    d, _ = synth_small
+    eng = _engine(d)
+    orc = OracleVacuum(d)
+    model = OrModel(orc)
+    stride = 100
+    b = w.ResidentBatch(eng, 512, stride)   # (max_queries: the `big` upload fills it, below)
+    try:
+        head = [f"t{i:07d}" for i in range(48)]
+        rare = next(t for t in (f"t{i:07d}" for i in range(2999, 0, -1)) if 0 < orc.df(t) < 128)
+        rng = random.Random(17)
+        small = [([rare], 10, False)]
+        big = [([h], 10, False) for h in head[:24]] * 5
+        big += [(rng.sample(head[:12], 2), 10, False) for _ in range(170)]
+        big += [(rng.sample(head, n), 10, False) for n in (17, 24, 40)]
+        big += [(head[:3], 10, True), (head[2:7], 64, True)]
+        big += [(head[:2], 100, False)]
+        # The query buffer starts at 80 B (sizeof(QueryIn)) * max_queries and an
+        # upload needs 80 B * nq + 4 B per term id of its queries over 16 terms:
+        # it grows only if nq reaches max_queries (or the long queries hold over
+        # 20 ids per free slot).  So fill the batch, with more of the head queries.
+        max_q = 512
+        big = big[:-6] + (big * 2)[:max_q - len(big)] + big[-6:]
+        n_ext = sum(len(t) for t, _, any_ in big if len(t) > 16 and not any_)
+        assert len(big) == max_q and n_ext == 17 + 24 + 40
+        assert 80 * len(big) + 4 * n_ext > 80 * max_q
+        want = {}   # computed once per distinct query, shared by the three runs
+
+        def expected(t, k, any_):
+            key = (tuple(t), k, any_)
+            if key not in want:
+                want[key] = [(dd, s) for s, dd in model.expected(t, k)] if any_ else orc.search(list(t), k)[0]
+            return want[key]
+
+        for items in (small, big, small):
+            qs = [eng.resolve(w.SearchQuery(list(t), n_results=k, match_any=any_))[0] for t, k, any_ in items]
+            b.upload((_capi.Query * len(qs))(*qs))
+            b.run()
+            hits, nh = b.fetch()
+            for i, (t, k, any_) in enumerate(items):
+                got = [(hits[i * stride + j].doc_id, hits[i * stride + j].score) for j in range(nh[i])]
+                assert got == expected(t, k, any_), (len(items), t, k, any_)
+        assert expected(*small[0]) and expected(*big[-1])
+    finally:
+        b.close()
+        eng.close()
+        orc.close()

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/wiser_hip.h"
+#include "dev_mem.h"
 #include "engine_types.h"
 #include "index.h"
 #include "kernels.h"
@@ -59,19 +60,12 @@ void set_last_error(const std::string& msg) { g_err = msg; }
 
 namespace {
 
-#define HIP_OK(expr)                                                                   \
-  do {                                                                                 \
-    hipError_t e_ = (expr);                                                            \
-    if (e_ != hipSuccess)                                                              \
-      throw std::runtime_error(std::string(#expr) + ": " + hipGetErrorString(e_));     \
-  } while (0)
-
+// fills dst from a host array (an empty one: a one-element placeholder); the bytes allocated
 template <class T, class A>
-uint64_t dev_upload(T** dst, const std::vector<T, A>& src) {
-  const size_t n = std::max<size_t>(src.size(), 1) * sizeof(T);
-  HIP_OK(hipMalloc(reinterpret_cast<void**>(dst), n));
-  if (!src.empty()) HIP_OK(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-  return n;
+uint64_t dev_upload(gpu::DevBuf<T>& dst, const std::vector<T, A>& src) {
+  dst.alloc(std::max<size_t>(src.size(), 1));
+  if (!src.empty()) HIP_OK(hipMemcpy(dst.get(), src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+  return dst.bytes();
 }
 
 // tuning knobs read once per wsr_open (unset or unparsable: the default)
@@ -88,34 +82,30 @@ double env_number(const char* name, double dflt) {
 struct wsr_handle {
   std::mutex mu;
   int device = 0;
-  hipStream_t stream = nullptr;
+  gpu::Stream stream;
   VacuumIndex idx;
   DocStore docs;                    // my.fdx / my.fdt when the index has them (snippets)
   std::unique_ptr<SkipRowCache> rows;   // decoded skip rows for the snippet stage
   std::mutex pool_mu;                   // wsr_search_batch's reusable batches
   std::vector<wsr_batch*> pool;
   IndexArgs args{};
-  uint8_t* d_blob = nullptr;
-  ListDev* d_lists = nullptr;
-  BlockDev* d_blocks = nullptr;
-  uint32_t* d_last = nullptr;
-  uint32_t* d_meta = nullptr;
-  uint8_t* d_c4 = nullptr;
-  double* d_cache = nullptr;
-  DenseEnt* d_dense = nullptr;
-  uint32_t* d_dense_rk = nullptr;   // the bitmap entries' rank records
-  uint32_t* d_bkt = nullptr;        // offset buckets (entries and offset bytes)
-  uint8_t* d_tf8 = nullptr;
-  uint8_t* d_plen = nullptr;
-  float* d_bmax = nullptr;
-  uint32_t* d_tails = nullptr;
-  uint8_t* d_pos_blob = nullptr;    // positions (opened with wsr_open_opts::positions)
-  PosDev* d_pos_lists = nullptr;
-  uint32_t* d_pos_pk = nullptr;
-  uint32_t* d_pos_tail = nullptr;
-  uint32_t* d_pos_start = nullptr;
-  uint8_t* d_blm = nullptr;
-  uint32_t* d_blm_hash = nullptr;
+  gpu::DevBuf<uint8_t> d_blob;
+  gpu::DevBuf<ListDev> d_lists;
+  gpu::DevBuf<BlockDev> d_blocks;
+  gpu::DevBuf<uint32_t> d_last, d_meta;
+  gpu::DevBuf<uint8_t> d_c4;
+  gpu::DevBuf<double> d_cache;
+  gpu::DevBuf<DenseEnt> d_dense;
+  gpu::DevBuf<uint32_t> d_dense_rk;   // the bitmap entries' rank records
+  gpu::DevBuf<uint32_t> d_bkt;        // offset buckets (entries and offset bytes)
+  gpu::DevBuf<uint8_t> d_tf8, d_plen;
+  gpu::DevBuf<float> d_bmax;
+  gpu::DevBuf<uint32_t> d_tails;
+  gpu::DevBuf<uint8_t> d_pos_blob;    // positions (opened with wsr_open_opts::positions)
+  gpu::DevBuf<PosDev> d_pos_lists;
+  gpu::DevBuf<uint32_t> d_pos_pk, d_pos_tail, d_pos_start;
+  gpu::DevBuf<uint8_t> d_blm;
+  gpu::DevBuf<uint32_t> d_blm_hash;
   bool positions = false;
   uint32_t dense_lists = 0;
   wsr_image_info info{};            // HBM bytes of the image's buffers
@@ -137,24 +127,21 @@ struct wsr_handle {
 
 struct wsr_batch {
   int max_q = 0, stride = 0, nq = 0;
-  QueryIn* d_q = nullptr;          // QueryIn[nq], then the term table of queries over kMaxTerms
-  size_t q_cap = 0;                // bytes of d_q
-  QueryPlan* d_plan = nullptr;
-  QueryDesc* d_desc = nullptr;     // lean queries' work records
-  PlanPart* d_part = nullptr;      // plan pass 1 -> 2 partial sums, per kPlanThreads queries
-  uint32_t* d_ctr = nullptr;
-  uint32_t* h_ctr = nullptr;       // pinned host copy of the counters (fetch)
-  Event* d_events = nullptr;
-  uint64_t ev_cap = 0;
-  uint32_t* d_evcnt = nullptr;
-  uint64_t item_cap = 0;
-  HitDev* d_hits = nullptr;
-  int32_t* d_nhits = nullptr;
-  uint32_t* d_qdone = nullptr;   // fused replay: completed items per query
-  uint32_t* d_itemq = nullptr;   // item -> query (capacity item_cap)
-  uint64_t* d_pub = nullptr;     // per item score floor (capacity item_cap)
-  uint32_t* d_stats = nullptr;   // per general workgroup, then per lean wave: survivors, blocks
-  uint32_t* d_ph = nullptr;      // phrase scratch, gen_cap * kPhraseScratch (lazily)
+  gpu::DevBuf<uint8_t> d_qb;       // QueryIn[nq], then the term table of queries over kMaxTerms (bytes)
+  QueryIn* d_q() const { return reinterpret_cast<QueryIn*>(d_qb.get()); }
+  gpu::DevBuf<QueryPlan> d_plan;
+  gpu::DevBuf<QueryDesc> d_desc;   // lean queries' work records
+  gpu::DevBuf<PlanPart> d_part;    // plan pass 1 -> 2 partial sums, per kPlanThreads queries
+  gpu::DevBuf<uint32_t> d_ctr;
+  gpu::PinnedBuf<uint32_t> h_ctr;  // pinned host copy of the counters (fetch)
+  gpu::DevBuf<Event> d_events;
+  gpu::DevBuf<uint32_t> d_evcnt, d_itemq;   // per item: its events, its query (sized together with d_pub)
+  gpu::DevBuf<HitDev> d_hits;
+  gpu::DevBuf<int32_t> d_nhits;
+  gpu::DevBuf<uint32_t> d_qdone;   // fused replay: completed items per query
+  gpu::DevBuf<uint64_t> d_pub;     // per item score floor
+  gpu::DevBuf<uint32_t> d_stats;   // per general workgroup, then per lean wave: survivors, blocks
+  gpu::DevBuf<uint32_t> d_ph;      // phrase scratch, gen_cap * kPhraseScratch (lazily)
   bool has_phrase = false;       // the uploaded queries include a phrase query
   bool gen_phrase = false;       // ... one of the general class (segment_kernel's phrase instance)
   bool has_conj_lean = true;     // the host's class rule found a conjunctive lean query
@@ -171,11 +158,9 @@ struct wsr_batch {
   // doc-range shard exchange (wsr_shard_step): per owner a region of {count,
   // offset} pairs + an event slot, owner-major to send, shard-major received;
   // allocated on first use
-  Event* d_xsend = nullptr;
-  Event* d_xrecv = nullptr;
-  uint64_t x_slots = 0;     // region events * pairs the two exchange buffers were sized for
+  gpu::DevBuf<Event> d_xsend, d_xrecv;   // region events * pairs each
   int x_pairs = 0;
-  hipEvent_t xev[2] = {nullptr, nullptr};   // emission done -> comm stream; exchange done -> replay
+  gpu::Event xev[2];   // emission done -> comm stream; exchange done -> replay
   std::atomic<bool> x_pending{false};   // a shard step's exchange + owner replay (xev[1]) not yet joined
   // exchanges asked of the communicator's worker thread for this batch, and
   // those it has enqueued (xev[1] recorded): xev[1] is only waited on once
@@ -205,15 +190,12 @@ struct wsr_batch {
   int or_nt_max = 0;             // the most resolved terms of one of them
   bool or_narrow = false, or_wide = false;   // some k <= kMaxK / > kMaxK among them
   bool has_or = false;           // the uploaded queries include an OR query (even an empty one)
-  OrQuery* d_orq = nullptr;
-  size_t orq_cap = 0;            // entries
-  OrItem* d_oritem = nullptr;
-  uint32_t* d_orevcnt = nullptr;
-  size_t oritem_cap = 0;         // entries of both
-  Event* d_orev = nullptr;
-  uint64_t orev_cap = 0;
-  unsigned long long* d_orstat = nullptr;   // kNumOrStats counters of the last run
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // [4]: lean kernel end
+  gpu::DevBuf<OrQuery> d_orq;
+  gpu::DevBuf<OrItem> d_oritem;
+  gpu::DevBuf<uint32_t> d_orevcnt;   // (sized together with d_oritem)
+  gpu::DevBuf<Event> d_orev;
+  gpu::DevBuf<unsigned long long> d_orstat;   // kNumOrStats counters of the last run
+  gpu::Event ev[5];   // (timing events) [4]: lean kernel end
   // Each batch runs on its own streams, so consecutive batches overlap on the
   // device (one's plan and first items under the other's last items); the
   // general kernel goes to st2, forked from and joined back into st.  HIP maps
@@ -225,8 +207,8 @@ struct wsr_batch {
   // alternating between two (with two streams per batch the C3 headline fell
   // from 21.7 to 18.9 M q/s and C2 from 35.0 to 29.6 M at unchanged per-batch
   // kernel times, profiles/r04a_bench.json).
-  hipStream_t st = nullptr, st2 = nullptr, st_pad = nullptr;
-  hipEvent_t fork = nullptr, join = nullptr, join_ph = nullptr;
+  gpu::Stream st, st2, st_pad;   // (created in this order, wsr_batch_create; nothing relies on the order they go in)
+  gpu::Event fork, join, join_ph;
   bool ran = false;
 };
 static void replay_flush(wsr_comm* c, const wsr_batch* upto);
@@ -357,75 +339,75 @@ int wsr_open(const char* dir, const wsr_open_opts* opts, wsr_handle** out) {
     HostImage img = build_image(h->idx, lo, hi, std::min(threads, 32), dense_div, h->positions, dense_budget,
                                 bloom_factor > 0, hbm_free);
     if (img.has_blooms) {   // (counted with the position boxes)
-      h->info.pos_bytes += dev_upload(&h->d_blm, img.blm);
-      h->info.pos_bytes += dev_upload(&h->d_blm_hash, img.blm_hash);
-      h->args.blm = reinterpret_cast<const uint4*>(h->d_blm);
-      h->args.blm_hash = reinterpret_cast<const uint2*>(h->d_blm_hash);
+      h->info.pos_bytes += dev_upload(h->d_blm, img.blm);
+      h->info.pos_bytes += dev_upload(h->d_blm_hash, img.blm_hash);
+      h->args.blm = reinterpret_cast<const uint4*>(h->d_blm.get());
+      h->args.blm_hash = reinterpret_cast<const uint2*>(h->d_blm_hash.get());
       h->args.blm_bits = img.blm_bits;
       h->args.blm_hashes = img.blm_hashes;
       h->args.bloom_factor = bloom_factor;
       big_vector<uint8_t>().swap(img.blm);
     }
     if (h->positions) {
-      h->info.pos_bytes += dev_upload(&h->d_pos_blob, img.pos_blob);
-      h->info.pos_bytes += dev_upload(&h->d_pos_lists, img.pos_lists);
-      h->info.pos_bytes += dev_upload(&h->d_pos_pk, img.pos_pk);
-      h->info.pos_bytes += dev_upload(&h->d_pos_tail, img.pos_tail);
-      h->info.pos_bytes += dev_upload(&h->d_pos_start, img.pos_start);
-      h->args.pos_blob = h->d_pos_blob;
-      h->args.pos_lists = h->d_pos_lists;
-      h->args.pos_pk = reinterpret_cast<const uint2*>(h->d_pos_pk);
-      h->args.pos_tail = h->d_pos_tail;
-      h->args.pos_start = reinterpret_cast<const uint2*>(h->d_pos_start);
+      h->info.pos_bytes += dev_upload(h->d_pos_blob, img.pos_blob);
+      h->info.pos_bytes += dev_upload(h->d_pos_lists, img.pos_lists);
+      h->info.pos_bytes += dev_upload(h->d_pos_pk, img.pos_pk);
+      h->info.pos_bytes += dev_upload(h->d_pos_tail, img.pos_tail);
+      h->info.pos_bytes += dev_upload(h->d_pos_start, img.pos_start);
+      h->args.pos_blob = h->d_pos_blob.get();
+      h->args.pos_lists = h->d_pos_lists.get();
+      h->args.pos_pk = reinterpret_cast<const uint2*>(h->d_pos_pk.get());
+      h->args.pos_tail = h->d_pos_tail.get();
+      h->args.pos_start = reinterpret_cast<const uint2*>(h->d_pos_start.get());
       h->pos_bytes = img.pos_list_bytes;
       std::vector<uint8_t>().swap(img.pos_blob);
       std::vector<uint32_t>().swap(img.pos_start);
     }
-    h->info.dense_bytes = dev_upload(&h->d_dense, img.dense);
-    h->info.dense_bytes += dev_upload(&h->d_dense_rk, img.dense_rank);
-    h->info.dense_bytes += dev_upload(&h->d_bkt, img.bkt);
-    h->info.tf8_bytes = dev_upload(&h->d_tf8, img.tf8);
+    h->info.dense_bytes = dev_upload(h->d_dense, img.dense);
+    h->info.dense_bytes += dev_upload(h->d_dense_rk, img.dense_rank);
+    h->info.dense_bytes += dev_upload(h->d_bkt, img.bkt);
+    h->info.tf8_bytes = dev_upload(h->d_tf8, img.tf8);
     h->dense_lists = img.dense_lists;
     h->info.dense_lists = img.dense_lists;
     h->info.n_lists = static_cast<uint32_t>(img.lists.size());
-    h->args.dense = h->d_dense;
-    h->args.dense_rk = h->d_dense_rk;
-    h->args.bkt = reinterpret_cast<const uint2*>(h->d_bkt);
-    h->args.tf8 = h->d_tf8;
+    h->args.dense = h->d_dense.get();
+    h->args.dense_rk = h->d_dense_rk.get();
+    h->args.bkt = reinterpret_cast<const uint2*>(h->d_bkt.get());
+    h->args.tf8 = h->d_tf8.get();
     h->args.dense_span = img.dense_span;
     h->args.dense_ratio = dense_ratio;
     h->args.seg_cap = kSegCost;
-    h->info.blob_bytes = dev_upload(&h->d_blob, img.blob);
-    h->info.plen_bytes = dev_upload(&h->d_plen, img.plen);
-    h->args.plen = h->d_plen;
-    h->info.dir_bytes += dev_upload(&h->d_bmax, img.bmax);
-    h->args.bmax = h->d_bmax;
-    h->info.dir_bytes += dev_upload(&h->d_tails, img.tails);
-    h->args.tails = h->d_tails;
-    h->info.dir_bytes += dev_upload(&h->d_lists, img.lists);
-    h->info.dir_bytes += dev_upload(&h->d_blocks, img.blocks);
-    h->info.dir_bytes += dev_upload(&h->d_last, img.blk_last);
-    h->info.dir_bytes += dev_upload(&h->d_meta, img.blk_meta);
-    h->info.dir_bytes += dev_upload(&h->d_c4, h->idx.char4_lengths());
+    h->info.blob_bytes = dev_upload(h->d_blob, img.blob);
+    h->info.plen_bytes = dev_upload(h->d_plen, img.plen);
+    h->args.plen = h->d_plen.get();
+    h->info.dir_bytes += dev_upload(h->d_bmax, img.bmax);
+    h->args.bmax = h->d_bmax.get();
+    h->info.dir_bytes += dev_upload(h->d_tails, img.tails);
+    h->args.tails = h->d_tails.get();
+    h->info.dir_bytes += dev_upload(h->d_lists, img.lists);
+    h->info.dir_bytes += dev_upload(h->d_blocks, img.blocks);
+    h->info.dir_bytes += dev_upload(h->d_last, img.blk_last);
+    h->info.dir_bytes += dev_upload(h->d_meta, img.blk_meta);
+    h->info.dir_bytes += dev_upload(h->d_c4, h->idx.char4_lengths());
     std::vector<double> cache(h->idx.bm25_cache(), h->idx.bm25_cache() + 256);
-    dev_upload(&h->d_cache, cache);
+    dev_upload(h->d_cache, cache);
     h->lists = img.lists;
     h->blocks.assign(img.blocks.begin(), img.blocks.end());
     h->meta.assign(img.blk_meta.begin(), img.blk_meta.end());
     h->list_bytes = img.list_bytes;
-    h->args.blob = h->d_blob;
-    h->args.lists = h->d_lists;
-    h->args.blocks = h->d_blocks;
-    h->args.blk_last = h->d_last;
-    h->args.blk_meta = h->d_meta;
-    h->args.c4 = h->d_c4;
-    h->args.cache = h->d_cache;
+    h->args.blob = h->d_blob.get();
+    h->args.lists = h->d_lists.get();
+    h->args.blocks = h->d_blocks.get();
+    h->args.blk_last = h->d_last.get();
+    h->args.blk_meta = h->d_meta.get();
+    h->args.c4 = h->d_c4.get();
+    h->args.cache = h->d_cache.get();
     h->args.n_c4 = static_cast<uint32_t>(h->idx.char4_lengths().size());
     h->args.n_lists = static_cast<uint32_t>(img.lists.size());
     h->args.doc_lo = lo;
     h->args.doc_hi = hi;
     h->args.avg = h->idx.avg_length();
-    HIP_OK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    h->stream = gpu::make_stream();
 
     hipDeviceProp_t prop;
     HIP_OK(hipGetDeviceProperties(&prop, dev));
@@ -454,8 +436,7 @@ int wsr_open(const char* dir, const wsr_open_opts* opts, wsr_handle** out) {
     // batches -2 %, so they keep the resident grid: profiles/r05/leg_ab.txt r05u-w)
     h->lean_wgs_two = prop.multiProcessorCount * std::min(locc + 1, 16);
   } catch (const std::exception& e) {
-    wsr_close(h.release());
-    return fail(WSR_E_HIP, e.what());
+    return fail(WSR_E_HIP, e.what());   // (h goes with what it got)
   }
   *out = h.release();
   return WSR_OK;
@@ -465,20 +446,7 @@ void wsr_close(wsr_handle* h) {
   if (!h) return;
   for (wsr_batch* b : h->pool) wsr_batch_destroy(h, b);
   h->pool.clear();
-  if (h->stream) { (void)hipStreamSynchronize(h->stream); (void)hipStreamDestroy(h->stream); }
-
-  for (void* p : {static_cast<void*>(h->d_blob), static_cast<void*>(h->d_lists),
-                  static_cast<void*>(h->d_blocks), static_cast<void*>(h->d_last),
-                  static_cast<void*>(h->d_meta),
-                  static_cast<void*>(h->d_c4), static_cast<void*>(h->d_cache),
-                  static_cast<void*>(h->d_dense), static_cast<void*>(h->d_dense_rk),
-                  static_cast<void*>(h->d_bkt), static_cast<void*>(h->d_tf8),
-                  static_cast<void*>(h->d_plen), static_cast<void*>(h->d_bmax), static_cast<void*>(h->d_tails),
-                  static_cast<void*>(h->d_pos_blob), static_cast<void*>(h->d_pos_lists),
-                  static_cast<void*>(h->d_pos_pk), static_cast<void*>(h->d_pos_tail),
-                  static_cast<void*>(h->d_pos_start), static_cast<void*>(h->d_blm),
-                  static_cast<void*>(h->d_blm_hash)})
-    if (p) (void)hipFree(p);
+  if (h->stream) (void)hipStreamSynchronize(h->stream);
   delete h;
 }
 
@@ -683,29 +651,25 @@ int wsr_batch_create(wsr_handle* h, int32_t max_q, int32_t stride, wsr_batch** o
     HIP_OK(hipSetDevice(h->device));
     b->max_q = max_q;
     b->stride = stride;
-    b->q_cap = sizeof(QueryIn) * max_q;
-    HIP_OK(hipMalloc(&b->d_q, b->q_cap));
-    HIP_OK(hipMalloc(&b->d_plan, sizeof(QueryPlan) * max_q));
-    HIP_OK(hipMalloc(&b->d_desc, sizeof(QueryDesc) * max_q));
-    HIP_OK(hipMalloc(&b->d_part, sizeof(PlanPart) * ((max_q + kPlanThreads - 1) / kPlanThreads + 1)));
-    HIP_OK(hipMalloc(&b->d_ctr, sizeof(uint32_t) * (kNumCounters + kMaxOwners)));   // + shard fill counters
-    HIP_OK(hipHostMalloc(&b->h_ctr, sizeof(uint32_t) * kNumCounters));
-    HIP_OK(hipMalloc(&b->d_hits, sizeof(HitDev) * static_cast<size_t>(max_q) * stride));
-    HIP_OK(hipMalloc(&b->d_nhits, sizeof(int32_t) * max_q));
-    HIP_OK(hipMalloc(&b->d_qdone, sizeof(uint32_t) * max_q));
-    HIP_OK(hipMalloc(&b->d_stats, sizeof(uint32_t) * kStatStride *
-                                      (std::max(std::max(h->grid, h->gen_cap), 1) +   // (seg_grid <= gen_cap)
-                                       kLeanWaves * (std::max(h->lean_wgs_two, 1) + std::max(h->lean_wgs_ph, 1)))));
-    for (auto& e : b->ev) HIP_OK(hipEventCreate(&e));
-    HIP_OK(hipStreamCreateWithFlags(&b->st, hipStreamNonBlocking));
-    HIP_OK(hipStreamCreateWithFlags(&b->st2, hipStreamNonBlocking));
-    HIP_OK(hipStreamCreateWithFlags(&b->st_pad, hipStreamNonBlocking));
-    HIP_OK(hipEventCreateWithFlags(&b->fork, hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&b->join, hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&b->join_ph, hipEventDisableTiming));
+    b->d_qb.alloc(sizeof(QueryIn) * max_q);
+    b->d_plan.alloc(max_q);
+    b->d_desc.alloc(max_q);
+    b->d_part.alloc((max_q + kPlanThreads - 1) / kPlanThreads + 1);
+    b->d_ctr.alloc(kNumCounters + kMaxOwners);   // + shard fill counters
+    b->h_ctr.alloc(kNumCounters);
+    b->d_hits.alloc(static_cast<size_t>(max_q) * stride);
+    b->d_nhits.alloc(max_q);
+    b->d_qdone.alloc(max_q);
+    b->d_stats.alloc(static_cast<size_t>(kStatStride) *
+                     (std::max(std::max(h->grid, h->gen_cap), 1) +   // (seg_grid <= gen_cap)
+                      kLeanWaves * (std::max(h->lean_wgs_two, 1) + std::max(h->lean_wgs_ph, 1))));
+    for (auto& e : b->ev) e = gpu::make_event(true);
+    b->st = gpu::make_stream();   // (this order: see wsr_batch::st)
+    b->st2 = gpu::make_stream();
+    b->st_pad = gpu::make_stream();
+    for (gpu::Event* e : {&b->fork, &b->join, &b->join_ph}) *e = gpu::make_event();
   } catch (const std::exception& e) {
-    wsr_batch_destroy(h, b.release());
-    return fail(WSR_E_HIP, e.what());
+    return fail(WSR_E_HIP, e.what());   // (b goes with what it got)
   }
   *out = b.release();
   return WSR_OK;
@@ -717,27 +681,6 @@ void wsr_batch_destroy(wsr_handle* h, wsr_batch* b) {
   if (b->st) (void)hipStreamSynchronize(b->st);
   if (b->st2) (void)hipStreamSynchronize(b->st2);
   if (b->st_pad) (void)hipStreamSynchronize(b->st_pad);
-  for (void* p : {static_cast<void*>(b->d_q), static_cast<void*>(b->d_plan),
-                  static_cast<void*>(b->d_desc), static_cast<void*>(b->d_part),
-                  static_cast<void*>(b->d_ctr), static_cast<void*>(b->d_events),
-                  static_cast<void*>(b->d_evcnt), static_cast<void*>(b->d_hits),
-                  static_cast<void*>(b->d_nhits), static_cast<void*>(b->d_stats),
-                  static_cast<void*>(b->d_qdone), static_cast<void*>(b->d_itemq),
-                  static_cast<void*>(b->d_pub), static_cast<void*>(b->d_ph),
-                  static_cast<void*>(b->d_xsend), static_cast<void*>(b->d_xrecv),
-                  static_cast<void*>(b->d_orq), static_cast<void*>(b->d_oritem),
-                  static_cast<void*>(b->d_orevcnt), static_cast<void*>(b->d_orev),
-                  static_cast<void*>(b->d_orstat)})
-    if (p) (void)hipFree(p);
-  if (b->h_ctr) (void)hipHostFree(b->h_ctr);
-  for (auto& e : b->ev) if (e) (void)hipEventDestroy(e);
-  for (auto& e : b->xev) if (e) (void)hipEventDestroy(e);
-  if (b->fork) (void)hipEventDestroy(b->fork);
-  if (b->join) (void)hipEventDestroy(b->join);
-  if (b->join_ph) (void)hipEventDestroy(b->join_ph);
-  if (b->st) (void)hipStreamDestroy(b->st);
-  if (b->st2) (void)hipStreamDestroy(b->st2);
-  if (b->st_pad) (void)hipStreamDestroy(b->st_pad);
   delete b;
 }
 
@@ -941,64 +884,26 @@ int wsr_batch_upload(wsr_handle* h, wsr_batch* b, const wsr_query* q, int32_t nq
     HIP_OK(hipSetDevice(h->device));
     HIP_OK(hipStreamSynchronize(b->st));
     if (x_join(b)) HIP_OK(hipEventSynchronize(b->xev[1]));   // a shard step's exchange + replay
-    if (ev_need > b->ev_cap) {
-      if (b->d_events) HIP_OK(hipFree(b->d_events));
-      b->ev_cap = ev_need + ev_need / 4 + 4096;
-      HIP_OK(hipMalloc(&b->d_events, sizeof(Event) * b->ev_cap));
-    }
-    if (items_need > b->item_cap || !b->d_evcnt) {
-      if (b->d_evcnt) HIP_OK(hipFree(b->d_evcnt));
-      if (b->d_itemq) HIP_OK(hipFree(b->d_itemq));
-      if (b->d_pub) HIP_OK(hipFree(b->d_pub));
-      b->d_itemq = nullptr;
-      b->d_pub = nullptr;
-      b->item_cap = items_need + items_need / 4 + 1024;
-      HIP_OK(hipMalloc(&b->d_evcnt, sizeof(uint32_t) * b->item_cap));
-      HIP_OK(hipMalloc(&b->d_itemq, sizeof(uint32_t) * b->item_cap));
-      HIP_OK(hipMalloc(&b->d_pub, sizeof(uint64_t) * b->item_cap));
-    }
+    // (on-demand buffers: a failure leaves the buffer empty, so the next upload allocates again)
+    b->d_events.reserve(ev_need, ev_need + ev_need / 4 + 4096);
+    if (items_need > b->d_evcnt.size() || !b->d_evcnt)
+      gpu::alloc_group(items_need + items_need / 4 + 1024, b->d_evcnt, b->d_itemq, b->d_pub);
     if (has_phrase && !b->d_ph)   // one per general workgroup
-      HIP_OK(hipMalloc(&b->d_ph, sizeof(uint32_t) * kPhraseScratch * static_cast<size_t>(std::max(h->gen_cap, 1))));
-    if (q_bytes > b->q_cap) {   // (the term table of long queries follows the QueryIn array)
-      if (b->d_q) HIP_OK(hipFree(b->d_q));
-      b->d_q = nullptr;
-      b->q_cap = q_bytes + q_bytes / 4;
-      HIP_OK(hipMalloc(&b->d_q, b->q_cap));
-    }
+      b->d_ph.alloc(kPhraseScratch * static_cast<size_t>(std::max(h->gen_cap, 1)));
+    b->d_qb.reserve(q_bytes, q_bytes + q_bytes / 4);   // (the term table of long queries follows the QueryIn array)
     if (!orq.empty()) {   // (a batch without a disjunctive query allocates nothing here)
       if (or_items.size() > 0xFFFFFFFFull) return fail(WSR_E_LIMIT, "over 2^32 disjunctive work items");
-      if (orq.size() > b->orq_cap) {
-        if (b->d_orq) HIP_OK(hipFree(b->d_orq));
-        b->d_orq = nullptr;
-        b->orq_cap = 0;
-        HIP_OK(hipMalloc(&b->d_orq, sizeof(OrQuery) * (orq.size() + orq.size() / 4)));
-        b->orq_cap = orq.size() + orq.size() / 4;
-      }
-      if (or_items.size() > b->oritem_cap) {
-        if (b->d_oritem) HIP_OK(hipFree(b->d_oritem));
-        if (b->d_orevcnt) HIP_OK(hipFree(b->d_orevcnt));
-        b->d_oritem = nullptr;
-        b->d_orevcnt = nullptr;
-        b->oritem_cap = 0;
-        const size_t cap = or_items.size() + or_items.size() / 4 + 64;
-        HIP_OK(hipMalloc(&b->d_oritem, sizeof(OrItem) * cap));
-        HIP_OK(hipMalloc(&b->d_orevcnt, sizeof(uint32_t) * cap));
-        b->oritem_cap = cap;
-      }
-      if (or_ev > b->orev_cap) {
-        if (b->d_orev) HIP_OK(hipFree(b->d_orev));
-        b->d_orev = nullptr;
-        b->orev_cap = 0;
-        HIP_OK(hipMalloc(&b->d_orev, sizeof(Event) * (or_ev + or_ev / 4)));
-        b->orev_cap = or_ev + or_ev / 4;
-      }
-      if (!b->d_orstat) HIP_OK(hipMalloc(&b->d_orstat, sizeof(unsigned long long) * kNumOrStats));
+      b->d_orq.reserve(orq.size(), orq.size() + orq.size() / 4);
+      if (or_items.size() > b->d_oritem.size())
+        gpu::alloc_group(or_items.size() + or_items.size() / 4 + 64, b->d_oritem, b->d_orevcnt);
+      b->d_orev.reserve(or_ev, or_ev + or_ev / 4);
+      if (!b->d_orstat) b->d_orstat.alloc(kNumOrStats);
       HIP_OK(hipMemcpy(b->d_orq, orq.data(), sizeof(OrQuery) * orq.size(), hipMemcpyHostToDevice));
       HIP_OK(hipMemcpy(b->d_oritem, or_items.data(), sizeof(OrItem) * or_items.size(), hipMemcpyHostToDevice));
     }
-    if (nq) HIP_OK(hipMemcpy(b->d_q, in.data(), sizeof(QueryIn) * nq, hipMemcpyHostToDevice));
+    if (nq) HIP_OK(hipMemcpy(b->d_q(), in.data(), sizeof(QueryIn) * nq, hipMemcpyHostToDevice));
     if (!ext.empty())
-      HIP_OK(hipMemcpy(reinterpret_cast<char*>(b->d_q) + sizeof(QueryIn) * nq, ext.data(),
+      HIP_OK(hipMemcpy(reinterpret_cast<char*>(b->d_q()) + sizeof(QueryIn) * nq, ext.data(),
                        sizeof(int32_t) * ext.size(), hipMemcpyHostToDevice));
   } catch (const std::exception& e) {
     return fail(WSR_E_HIP, e.what());
@@ -1112,8 +1017,8 @@ static int batch_run(wsr_handle* h, wsr_batch* b, const ShardEmit* se, const Own
     const bool run_gen = se || !b->has_phrase || b->has_gen;
     b->ran_conj = run_conj;
     b->ran_gen = run_gen;
-    HIP_OK(launch_plan(pa, b->d_q, b->nq, b->d_plan, b->d_ctr, b->ev_cap,
-                       static_cast<uint32_t>(std::min<uint64_t>(b->item_cap, 0xFFFFFFFFull)),
+    HIP_OK(launch_plan(pa, b->d_q(), b->nq, b->d_plan, b->d_ctr, b->d_events.size(),
+                       static_cast<uint32_t>(std::min<uint64_t>(b->d_evcnt.size(), 0xFFFFFFFFull)),
                        run_conj ? kLeanWaves * b->lean_wgs : 0, b->has_phrase ? kLeanWaves * b->lean_wgs_ph : 0,
                        run_gen ? b->seg_grid : 0, fr, b->d_itemq, b->d_pub, b->d_desc, b->d_part, st));
     HIP_OK(hipEventRecord(b->ev[1], st));
@@ -1122,7 +1027,7 @@ static int batch_run(wsr_handle* h, wsr_batch* b, const ShardEmit* se, const Own
     HIP_OK(hipEventRecord(b->fork, st));
     HIP_OK(hipStreamWaitEvent(b->st2, b->fork, 0));
     if (run_gen)
-      HIP_OK(launch_segments(h->args, b->d_q, b->d_plan, b->nq, b->d_ctr, b->d_events, b->d_evcnt,
+      HIP_OK(launch_segments(h->args, b->d_q(), b->d_plan, b->nq, b->d_ctr, b->d_events, b->d_evcnt,
                              b->d_stats, b->seg_grid, fr, b->d_itemq, b->d_pub,
                              b->gen_phrase ? b->d_ph : nullptr, b->st2));
     uint32_t* lean_stats = b->d_stats + static_cast<size_t>(kStatStride) * b->seg_grid;
@@ -1137,7 +1042,7 @@ static int batch_run(wsr_handle* h, wsr_batch* b, const ShardEmit* se, const Own
       // deferred owner replay runs in the conjunctive launch only.)
       HIP_OK(hipStreamWaitEvent(b->st_pad, b->fork, 0));
       if (run_conj)
-        HIP_OK(launch_lean(h->args, b->d_q, b->d_plan, b->nq, b->d_ctr, b->d_events, b->d_evcnt, lean_stats,
+        HIP_OK(launch_lean(h->args, b->d_q(), b->d_plan, b->nq, b->d_ctr, b->d_events, b->d_evcnt, lean_stats,
                            b->lean_wgs, fr, b->d_itemq, b->d_pub, b->d_desc, false, b->two_conj, b->one_conj,
                            b->st_pad));
       if (pb) {   // the replay's end: behind the conjunctive launch that carried it
@@ -1147,11 +1052,11 @@ static int batch_run(wsr_handle* h, wsr_batch* b, const ShardEmit* se, const Own
       HIP_OK(hipEventRecord(b->join_ph, b->st_pad));
       FusedReplay frp = fr;
       frp.oj = OwnerJob{};
-      HIP_OK(launch_lean(h->args, b->d_q, b->d_plan, b->nq, b->d_ctr, b->d_events, b->d_evcnt,
+      HIP_OK(launch_lean(h->args, b->d_q(), b->d_plan, b->nq, b->d_ctr, b->d_events, b->d_evcnt,
                          lean_stats + static_cast<size_t>(kStatStride) * kLeanWaves * b->lean_wgs,
                          b->lean_wgs_ph, frp, b->d_itemq, b->d_pub, b->d_desc, true, b->two_ph, false, st));
     } else {
-      HIP_OK(launch_lean(h->args, b->d_q, b->d_plan, b->nq, b->d_ctr, b->d_events, b->d_evcnt, lean_stats,
+      HIP_OK(launch_lean(h->args, b->d_q(), b->d_plan, b->nq, b->d_ctr, b->d_events, b->d_evcnt, lean_stats,
                          b->lean_wgs, fr, b->d_itemq, b->d_pub, b->d_desc, false, b->two_conj, b->one_conj, st));
     }
     HIP_OK(hipEventRecord(b->ev[4], st));
@@ -1168,7 +1073,7 @@ static int batch_run(wsr_handle* h, wsr_batch* b, const ShardEmit* se, const Own
     if (b->has_phrase) HIP_OK(hipStreamWaitEvent(st, b->join_ph, 0));
     HIP_OK(hipEventRecord(b->ev[2], st));
     if (!se && b->has_wide)
-      HIP_OK(launch_wide_replay(b->d_q, b->d_plan, b->nq, b->d_events, b->d_evcnt, b->d_hits, b->stride,
+      HIP_OK(launch_wide_replay(b->d_q(), b->d_plan, b->nq, b->d_events, b->d_evcnt, b->d_hits, b->stride,
                                 b->d_nhits, st));
     if (b->n_or) {
       // the disjunctive queries, after the plan's writes of their (empty) rows
@@ -1267,6 +1172,7 @@ int wsr_batch_fetch_cols(wsr_handle* h, wsr_batch* b, wsr_hit* hits, int32_t* n_
   return batch_fetch(h, b, hits, n_hits, cols);
 }
 
+// (raw, not a PinnedBuf: the block's ownership crosses the C ABI to the caller)
 int wsr_pinned_alloc(uint64_t bytes, void** out) {
   if (!out) return fail(WSR_E_INVALID, "null argument");
   *out = nullptr;
@@ -1555,11 +1461,9 @@ using XJob = std::shared_ptr<XGroup>;
 constexpr int kXSlots = 4;       // exchange buffer sets in rotation
 constexpr size_t kReplayLag = 2;  // groups between a group's exchange and its deferred replays
 struct XSlot {
-  Event* send = nullptr;
-  Event* recv = nullptr;
-  uint64_t events = 0;
-  hipEvent_t xa = nullptr;            // the last all-to-all out of this slot done (comm stream)
-  std::vector<hipEvent_t> done;       // its group's owner replays done, one per batch
+  gpu::DevBuf<Event> send, recv;
+  gpu::Event xa;                      // the last all-to-all out of this slot done (comm stream)
+  std::vector<gpu::Event> done;       // its group's owner replays done, one per batch
   size_t n_done = 0;                  // (recorded)
   std::shared_ptr<XGroup> last;       // the group that used it last
 };
@@ -1588,8 +1492,8 @@ struct wsr_comm {
   ncclComm_t comm = nullptr;
   wsr_loopback* loop = nullptr;   // a loopback communicator (no RCCL)
   uint64_t loop_seq = 0;
-  hipEvent_t loop_ready = nullptr, loop_read = nullptr;
-  hipStream_t stream = nullptr;
+  gpu::Event loop_ready, loop_read;
+  gpu::Stream stream;
   int world = 0, rank = 0, device = 0;
   // WSR_HOST_TIMING=1: host time per phase of wsr_shard_step (enqueue only),
   // printed to stderr when the communicator closes
@@ -1783,10 +1687,11 @@ int wsr_comm_open(const uint8_t* id, int32_t world, int32_t rank, int32_t device
   int lo_prio = 0, hi_prio = 0;
   const bool prio = env_number("WSR_COMM_PRIORITY", 0) != 0 &&
                     hipDeviceGetStreamPriorityRange(&lo_prio, &hi_prio) == hipSuccess;
-  if ((prio ? hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, hi_prio)
-            : hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess) {
+  try {
+    c->stream = gpu::make_stream(prio ? &hi_prio : nullptr);
+  } catch (const std::exception& e) {
     (void)ncclCommDestroy(c->comm);
-    return fail(WSR_E_HIP, "hipStreamCreate failed");
+    return fail(WSR_E_HIP, e.what());
   }
   c->world = world;
   c->rank = rank;
@@ -1815,12 +1720,12 @@ int wsr_comm_open_loopback(wsr_loopback* l, int32_t rank, int32_t device, wsr_co
   if (hipSetDevice(device) != hipSuccess) return fail(WSR_E_HIP, "hipSetDevice failed");
   std::unique_ptr<wsr_comm> c(new wsr_comm());
   c->loop = l;
-  if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&c->loop_ready, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->loop_read, hipEventDisableTiming) != hipSuccess) {
-    if (c->loop_ready) (void)hipEventDestroy(c->loop_ready);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    return fail(WSR_E_HIP, "hipStreamCreate / hipEventCreate failed");
+  try {
+    c->stream = gpu::make_stream();
+    c->loop_ready = gpu::make_event();
+    c->loop_read = gpu::make_event();
+  } catch (const std::exception& e) {
+    return fail(WSR_E_HIP, e.what());
   }
   c->world = l->world;
   c->rank = rank;
@@ -1847,17 +1752,9 @@ void wsr_comm_close(wsr_comm* c) {
                  static_cast<unsigned long long>(c->steps), c->t_ns[0] / 1e3 / c->steps,
                  c->t_ns[1] / 1e3 / c->steps, c->t_ns[2] / 1e3 / c->steps, c->t_ns[3] / 1e3 / c->steps);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  for (XSlot& S : c->xs) {
+  for (XSlot& S : c->xs)
     for (size_t i = 0; i < S.n_done; ++i) (void)hipEventSynchronize(S.done[i]);   // (replays in lean kernels)
-    for (hipEvent_t e : S.done) (void)hipEventDestroy(e);
-    if (S.xa) (void)hipEventDestroy(S.xa);
-    if (S.send) (void)hipFree(S.send);
-    if (S.recv) (void)hipFree(S.recv);
-  }
-  if (c->comm) (void)ncclCommDestroy(c->comm);
-  if (c->loop_ready) (void)hipEventDestroy(c->loop_ready);
-  if (c->loop_read) (void)hipEventDestroy(c->loop_read);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
+  if (c->comm) (void)ncclCommDestroy(c->comm);   // (ahead of its stream, which goes with c)
   delete c;
 }
 
@@ -1869,7 +1766,7 @@ static int owner_replay_meta_on(wsr_handle* h, wsr_batch* b, int32_t q0, int32_t
     return fail(WSR_E_INVALID, "bad owner_replay_meta arguments");
   try {
     HIP_OK(hipSetDevice(h->device));
-    HIP_OK(launch_owner_replay_meta(b->d_q, q0, nq_owned, n_shards, d_rmeta, meta_stride, stride,
+    HIP_OK(launch_owner_replay_meta(b->d_q(), q0, nq_owned, n_shards, d_rmeta, meta_stride, stride,
                                     static_cast<const Event*>(d_recv), b->d_hits, b->stride, b->d_nhits,
                                     b->d_ctr, b->has_wide, st));
   } catch (const std::exception& e) {
@@ -1906,22 +1803,14 @@ static int check_step(wsr_handle* h, wsr_batch* b, int W, int32_t q_per_owner, i
 
 // The events that order a shard step's exchange against the batch's runs.
 static void ensure_xev(wsr_batch* b) {
-  if (!b->xev[0]) {
-    HIP_OK(hipEventCreateWithFlags(&b->xev[0], hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&b->xev[1], hipEventDisableTiming));
-  }
+  for (auto& e : b->xev) if (!e) e = gpu::make_event();
 }
 
 // The exchange buffers of b: send and receive, need events each.
 static void ensure_xbuf(wsr_batch* b, uint64_t need, int W) {
-  if (need > b->x_slots || W != b->x_pairs) {
+  if (need > b->d_xsend.size() || W != b->x_pairs) {
     if (x_join(b)) HIP_OK(hipEventSynchronize(b->xev[1]));
-    if (b->d_xsend) HIP_OK(hipFree(b->d_xsend));
-    if (b->d_xrecv) HIP_OK(hipFree(b->d_xrecv));
-    b->d_xsend = b->d_xrecv = nullptr;
-    HIP_OK(hipMalloc(&b->d_xsend, sizeof(Event) * need));
-    HIP_OK(hipMalloc(&b->d_xrecv, sizeof(Event) * need));
-    b->x_slots = need;
+    gpu::alloc_group(need, b->d_xsend, b->d_xrecv);
     b->x_pairs = W;
   }
   ensure_xev(b);
@@ -2107,27 +1996,17 @@ int wsr_shard_steps(wsr_handle* h, wsr_batch* const* bs, int32_t n, wsr_comm* c,
       while (!S.last->enq.load(std::memory_order_acquire)) std::this_thread::yield();
     }
     const uint64_t need = run * static_cast<uint64_t>(W);
-    if (need > S.events) {
+    if (need > S.send.size()) {
       if (S.last) {
         HIP_OK(hipEventSynchronize(S.xa));
         for (size_t i = 0; i < S.n_done; ++i) HIP_OK(hipEventSynchronize(S.done[i]));
         S.last.reset();
         S.n_done = 0;
       }
-      if (S.send) HIP_OK(hipFree(S.send));
-      if (S.recv) HIP_OK(hipFree(S.recv));
-      S.send = S.recv = nullptr;
-      S.events = 0;
-      HIP_OK(hipMalloc(&S.send, sizeof(Event) * need));
-      HIP_OK(hipMalloc(&S.recv, sizeof(Event) * need));
-      S.events = need;
+      gpu::alloc_group(need, S.send, S.recv);
     }
-    if (!S.xa) HIP_OK(hipEventCreateWithFlags(&S.xa, hipEventDisableTiming));
-    while (S.done.size() < static_cast<size_t>(n)) {
-      hipEvent_t e;
-      HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      S.done.push_back(e);
-    }
+    if (!S.xa) S.xa = gpu::make_event();
+    while (S.done.size() < static_cast<size_t>(n)) S.done.push_back(gpu::make_event());
     // the deferred replays this group's lean kernels take
     if (c->defer && c->pend.size() >= kReplayLag) {
       P = c->pend.front();
@@ -2141,7 +2020,7 @@ int wsr_shard_steps(wsr_handle* h, wsr_batch* const* bs, int32_t n, wsr_comm* c,
         if (P->queued[i]) continue;
         if (pb->has_wide) continue;   // (the LDS heap: on the communicator's stream)
         const Event* recv = SP.recv + rP * i;
-        oj[i] = OwnerJob{pb->d_q, reinterpret_cast<const int32_t*>(recv), recv + meta_events, pb->d_hits,
+        oj[i] = OwnerJob{pb->d_q(), reinterpret_cast<const int32_t*>(recv), recv + meta_events, pb->d_hits,
                          pb->d_nhits, pb->d_ctr, runP * (sizeof(Event) / sizeof(int32_t)), runP,
                          c->rank * P->qpr, P->qpr, W, pb->stride};
       }
@@ -2315,7 +2194,8 @@ static wsr_batch* take_host_replay(wsr_handle* h, const wsr_batch* b, OwnerJob* 
     pb->hdef.store(nullptr);
     const uint64_t region = region_events_of(pb->x_qpr, pb->x_slot);
     const uint64_t meta_events = (static_cast<uint64_t>(pb->x_qpr) + 1) / 2;
-    *oj = OwnerJob{pb->d_q, reinterpret_cast<const int32_t*>(pb->d_xrecv), pb->d_xrecv + meta_events, pb->d_hits,
+    const Event* recv = pb->d_xrecv;
+    *oj = OwnerJob{pb->d_q(), reinterpret_cast<const int32_t*>(recv), recv + meta_events, pb->d_hits,
                    pb->d_nhits, pb->d_ctr, region * (sizeof(Event) / sizeof(int32_t)), region,
                    pb->hdef_rank * pb->x_qpr, pb->x_qpr, pb->x_world, pb->stride};
     return pb;
@@ -2385,15 +2265,13 @@ int wsr_debug_decode_block(wsr_handle* h, int32_t id, int32_t block, int32_t whi
   const BlockDev& bd = h->blocks[L.blk0 + block];
   const uint32_t cnt = static_cast<uint32_t>(block) == L.nblk - 1 ? L.tail_cnt : 128u;
   try {
-    uint32_t* d_out = nullptr;
-    HIP_OK(hipMalloc(&d_out, 128 * sizeof(uint32_t)));
-    const uint8_t* p = h->d_blob + L.base + (which ? bd.tf_rel : bd.doc_rel);
+    gpu::DevBuf<uint32_t> d_out;
+    d_out.alloc(128);
+    const uint8_t* p = h->d_blob.get() + L.base + (which ? bd.tf_rel : bd.doc_rel);
     const uint32_t bits = which ? (h->meta[L.blk0 + block] >> 8) : (h->meta[L.blk0 + block] & 0xFF);
-    hipError_t e = launch_decode_probe(p, bits, cnt, which == 0, bd.prev, d_out, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e == hipSuccess) e = hipMemcpy(out, d_out, 128 * sizeof(uint32_t), hipMemcpyDeviceToHost);
-    (void)hipFree(d_out);
-    HIP_OK(e);
+    HIP_OK(launch_decode_probe(p, bits, cnt, which == 0, bd.prev, d_out, h->stream));
+    HIP_OK(hipStreamSynchronize(h->stream));
+    HIP_OK(hipMemcpy(out, d_out, d_out.bytes(), hipMemcpyDeviceToHost));
   } catch (const std::exception& ex) {
     return fail(WSR_E_HIP, ex.what());
   }

@@ -33,6 +33,7 @@
 #include <unistd.h>
 
 #include "../../include/wiser_hip.h"
+#include "dev_mem.h"
 
 namespace wiser {
 void set_last_error(const std::string& msg);   // engine.cc
@@ -148,8 +149,8 @@ struct wsr_server {
   bool fstop = false;
   // fetch buffers of one batch (completer only), page-locked so the result
   // copies are DMA'd
-  wsr_hit* hits = nullptr;
-  int32_t* nh = nullptr;
+  gpu::PinnedBuf<wsr_hit> hits;
+  gpu::PinnedBuf<int32_t> nh;
   std::vector<wsr_query> qbuf;       // dispatcher only
   std::atomic<uint64_t> batches{0}, queries{0};
   // latency breakdown (ns): submit -> launch summed over queries; launch ->
@@ -389,17 +390,15 @@ int wsr_server_open(wsr_handle* h, int32_t max_batch, int32_t window_us, wsr_ser
     // server's batches are latency-bound (WSR_SERVER_ITEM_BLOCKS)
     if (rc == WSR_OK) rc = wsr_batch_set_item_blocks(h, sl.b, item_blocks);
     if (rc != WSR_OK) {
-      for (auto& x : s->slots)
-        if (x.b) wsr_batch_destroy(h, x.b);
+      wsr_server_close(s.release());   // (no thread started yet: it destroys the batches made so far)
       return rc;
     }
   }
-  if (hipHostMalloc(reinterpret_cast<void**>(&s->hits),
-                    sizeof(wsr_hit) * static_cast<size_t>(max_batch) * WSR_SERVER_MAX_K) != hipSuccess ||
-      hipHostMalloc(reinterpret_cast<void**>(&s->nh), sizeof(int32_t) * static_cast<size_t>(max_batch)) !=
-          hipSuccess) {
-    for (auto& x : s->slots) wsr_batch_destroy(h, x.b);
-    if (s->hits) (void)hipHostFree(s->hits);
+  try {
+    s->hits.alloc(static_cast<size_t>(max_batch) * WSR_SERVER_MAX_K);
+    s->nh.alloc(static_cast<size_t>(max_batch));
+  } catch (const std::exception&) {
+    wsr_server_close(s.release());
     return WSR_E_HIP;
   }
   s->worker = std::thread([p = s.get()] { p->run(); });
@@ -418,8 +417,6 @@ void wsr_server_close(wsr_server* s) {
   if (s->completer.joinable()) s->completer.join();   // retires what is in flight
   for (auto& sl : s->slots)
     if (sl.b) wsr_batch_destroy(s->h, sl.b);
-  if (s->hits) (void)hipHostFree(s->hits);
-  if (s->nh) (void)hipHostFree(s->nh);
   delete s;
 }
 
