@@ -435,6 +435,29 @@ int wsr_debug_decode_block(wsr_handle* h, int32_t list_id, int32_t block, int32_
 int wsr_debug_wg_stats(wsr_handle* h, wsr_batch* b, uint32_t* out, int32_t max_words,
                        int32_t* n_wg, int32_t* stride);
 
+/* The launch class of a batch (test hook; host state only, nothing is
+ * launched, copied or waited for): *flags receives the class flags the batch's
+ * last wsr_batch_upload set -- they pick the kernel instances a run launches --
+ * and which of the conditional launches its last run made (both set before
+ * the first run). */
+enum {
+  WSR_CLASS_TWO_CONJ = 1 << 0,       /* every conjunctive query: two terms (or empty), k <= 64:
+                                        the two-term lean instance */
+  WSR_CLASS_ONE_CONJ = 1 << 1,       /* every conjunctive query: one term (or empty), and not
+                                        all of them empty: the single-term lean instance */
+  WSR_CLASS_HAS_PHRASE = 1 << 2,     /* a phrase query: the phrase lean instance is launched */
+  WSR_CLASS_TWO_PH = 1 << 3,         /* every phrase query: k <= 64 (the narrow phrase instance) */
+  WSR_CLASS_HAS_WIDE = 1 << 4,       /* a conjunctive or phrase query with k > 64: the wide replay */
+  WSR_CLASS_GEN_PHRASE = 1 << 5,     /* a phrase query of the general class (the general
+                                        kernel's phrase instance) */
+  WSR_CLASS_HAS_CONJ_LEAN = 1 << 6,  /* the host's class rule found a conjunctive lean query */
+  WSR_CLASS_HAS_GEN = 1 << 7,        /* ... a general one */
+  WSR_CLASS_HAS_OR = 1 << 8,         /* a disjunctive query (even an empty one) */
+  WSR_CLASS_RAN_CONJ = 1 << 9,       /* the last run launched the conjunctive lean kernel */
+  WSR_CLASS_RAN_GEN = 1 << 10        /* ... the general kernel */
+};
+int wsr_debug_batch_class(wsr_handle* h, wsr_batch* b, uint32_t* flags);
+
 /* Fault injection (tests of the error paths): the next n batch runs -- plain
  * or the emission of a shard step -- fail with WSR_E_HIP before they enqueue
  * anything.  n = 0 clears it. */

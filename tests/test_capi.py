@@ -47,6 +47,21 @@ def test_null_arguments_are_errors(built):
     _capi.lib.wsr_close(None)  # no-op
 
 
+def test_batch_class_hook(built):
+    """wsr_debug_batch_class is exported, refuses null arguments, and the
+    mirror's bit names are the header's WSR_CLASS_* constants."""
+    import re
+    from wiser_amd import _capi
+    assert hasattr(_capi.lib, "wsr_debug_batch_class")
+    assert "wsr_debug_batch_class" in _capi.header_symbols()
+    assert _capi.lib.wsr_debug_batch_class(None, None, None) == _capi.E_INVALID
+    assert b"null argument" in _capi.lib.wsr_last_error()
+    text = open(_capi.HEADER).read()
+    bits = {m.group(1).lower(): 1 << int(m.group(2))
+            for m in re.finditer(r"\bWSR_CLASS_(\w+)\s*=\s*1\s*<<\s*(\d+)", text)}
+    assert bits == _capi.CLASS_BITS and len(bits) == 11
+
+
 def test_struct_layouts(built, tmp_path):
     """ctypes mirrors agree with include/wiser_hip.h as compiled by gcc."""
     import subprocess

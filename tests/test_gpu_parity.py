@@ -230,21 +230,8 @@ def test_large_tf_dense_escape(tmp_path, mode):
     (pack blocks and the VInts tail)."""
     from oracle.oracle import OracleVacuum
     import wiser_amd as w
-    ld = tmp_path / "big_tf.linedoc"
-    rng = random.Random(5)
-    with open(ld, "w") as f:
-        f.write("FIELDS_HEADER_INDICATOR###\tdoctitle\tbody\ttokenized\n")
-        for i in range(300):
-            toks = ["x"] * rng.choice([1, 2, 254, 255, 256, 600])
-            if i % 2 == 0:
-                toks += ["y"] * rng.randint(1, 3)
-            if i % 7 == 0:
-                toks += ["z"] * 300
-            toks += [f"w{i}"]
-            f.write(f"t\t{' '.join(toks)}\t{' '.join(toks)}\n")
-    d = tmp_path / "idx"
-    d.mkdir()
-    w.build_from_linedoc(str(ld), str(d), "TOKEN_ONLY")
+    from edge_corpora import build_large_tf_index
+    d = build_large_tf_index(tmp_path)
     eng = _engine(str(d), mode)
     orc = OracleVacuum(str(d))
     _check(eng, orc, [["x"], ["y", "x"], ["x", "y"], ["z", "x"], ["y", "z", "x"], ["w7", "x"],

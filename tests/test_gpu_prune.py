@@ -23,30 +23,8 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope="module")
 def tie_index(built, tmp_path_factory):
-    import wiser_amd as w
-    root = str(tmp_path_factory.mktemp("ties"))
-    path = os.path.join(root, "ties.linedoc")
-    rng = random.Random(5)
-    with open(path, "w") as f:
-        f.write("FIELDS_HEADER_INDICATOR###\tdoctitle\tbody\ttokenized\n")
-        for i in range(20000):
-            toks = ["a"] * rng.choice([1, 1, 1, 2, 3])
-            if rng.random() < 0.8:
-                toks += ["b"] * rng.choice([1, 1, 2])
-            if rng.random() < 0.5:
-                toks += ["c"] * rng.choice([1, 2, 3])
-            if rng.random() < 0.3:
-                toks += ["d"]
-            if i == 7777:
-                toks += ["c"] * 300   # above the tf8 escape: c's tf bound is 303
-            n = rng.choice([8, 16, 24, 64])
-            toks += [f"f{j}" for j in range(max(0, n - len(toks)))]
-            rng.shuffle(toks)
-            f.write(f"t\t{' '.join(toks)}\t{' '.join(toks)}\n")
-    d = os.path.join(root, "idx")
-    os.makedirs(d)
-    w.build_from_linedoc(path, d, "TOKEN_ONLY")
-    return d
+    from edge_corpora import build_tie_index
+    return build_tie_index(tmp_path_factory.mktemp("ties"))
 
 
 @pytest.mark.parametrize("mode", sorted(DENSE_MODES))

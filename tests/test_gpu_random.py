@@ -7,42 +7,10 @@ import random
 
 import pytest
 
+from edge_corpora import write_skewed_linedoc as _corpus
 from test_gpu_parity import DENSE_MODES, _engine
 
 pytestmark = pytest.mark.gpu
-
-
-def _corpus(path, seed):
-    """WITH_POSITIONS linedoc; returns the vocabulary."""
-    rng = random.Random(seed)
-    vocab = [f"v{i}" for i in range(rng.choice([5, 30, 300]))]
-    fixed = {f"x{n}": n for n in (1, 2, 127, 128, 129, 255, 256, 300)}   # term -> df
-    n_docs = rng.choice([300, 700, 1500])
-    docs = [[] for _ in range(n_docs)]
-    for t, df in fixed.items():
-        for d in rng.sample(range(n_docs), min(df, n_docs)):
-            docs[d].append(t)
-    weights = [1.0 / (i + 1) for i in range(len(vocab))]
-    for d in range(n_docs):
-        docs[d] += rng.choices(vocab, weights, k=rng.choice([0, 1, 3, 20, 80]))
-        if d % 97 == 0:
-            docs[d] += ["heavy"] * 300          # tf >= 255
-        rng.shuffle(docs[d])
-        if not docs[d]:
-            docs[d] = ["lonely"]
-    with open(path, "w") as f:
-        f.write("FIELDS_HEADER_INDICATOR###\tdoctitle\tbody\ttokenized\toffsets\tpositions\n")
-        for seq in docs:
-            occ, offs, at = {}, {}, 0
-            for p, w in enumerate(seq):
-                occ.setdefault(w, []).append(p)
-                offs.setdefault(w, []).append((at, at + len(w)))
-                at += len(w) + 1
-            toks = list(occ)
-            off_col = "".join("".join(f"{s},{e};" for s, e in offs[w]) + "." for w in toks)
-            pos_col = "".join("".join(f"{p};" for p in occ[w]) + "." for w in toks)
-            f.write(f"t\t{' '.join(seq)}\t{' '.join(toks)}\t{off_col}\t{pos_col}\n")
-    return vocab + list(fixed) + ["heavy", "lonely", "absent-term"]
 
 
 @pytest.mark.parametrize("seed", [1, 2, 3, 4, 5, 6, 7, 8])

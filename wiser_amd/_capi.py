@@ -31,6 +31,11 @@ ERRORS = {-1: "WSR_E_INVALID", -2: "WSR_E_IO", -3: "WSR_E_HIP", -4: "WSR_E_LIMIT
 QUERY_PHRASE = 1
 QUERY_OR = 2              # a doc matches when it holds at least one of the terms
 
+# wsr_debug_batch_class: the WSR_CLASS_* bits, by the name of the batch's field
+CLASS_BITS = {"two_conj": 1 << 0, "one_conj": 1 << 1, "has_phrase": 1 << 2, "two_ph": 1 << 3,
+              "has_wide": 1 << 4, "gen_phrase": 1 << 5, "has_conj_lean": 1 << 6, "has_gen": 1 << 7,
+              "has_or": 1 << 8, "ran_conj": 1 << 9, "ran_gen": 1 << 10}
+
 
 class OpenOpts(C.Structure):
     _fields_ = [("device", C.c_int32), ("doc_lo", C.c_uint32), ("doc_hi", C.c_uint32),
@@ -150,6 +155,7 @@ _sigs = {
     "wsr_shard_step_replay_deferred": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _P]),
     "wsr_debug_wg_stats": (C.c_int, [_P, _P, C.POINTER(C.c_uint32), C.c_int32,
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "wsr_debug_batch_class": (C.c_int, [_P, _P, C.POINTER(C.c_uint32)]),
     "wsr_debug_fail_runs": (C.c_int, [C.c_int32]),
     "wsr_debug_decode_block": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32,
                                          C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]),

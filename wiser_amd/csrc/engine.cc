@@ -2301,6 +2301,17 @@ int wsr_debug_wg_stats(wsr_handle* h, wsr_batch* b, uint32_t* out, int32_t max_w
   return WSR_OK;
 }
 
+int wsr_debug_batch_class(wsr_handle* h, wsr_batch* b, uint32_t* flags) {
+  if (!h || !b || !flags) return fail(WSR_E_INVALID, "null argument");
+  *flags = (b->two_conj ? WSR_CLASS_TWO_CONJ : 0u) | (b->one_conj ? WSR_CLASS_ONE_CONJ : 0u) |
+           (b->has_phrase ? WSR_CLASS_HAS_PHRASE : 0u) | (b->two_ph ? WSR_CLASS_TWO_PH : 0u) |
+           (b->has_wide ? WSR_CLASS_HAS_WIDE : 0u) | (b->gen_phrase ? WSR_CLASS_GEN_PHRASE : 0u) |
+           (b->has_conj_lean ? WSR_CLASS_HAS_CONJ_LEAN : 0u) | (b->has_gen ? WSR_CLASS_HAS_GEN : 0u) |
+           (b->has_or ? WSR_CLASS_HAS_OR : 0u) | (b->ran_conj ? WSR_CLASS_RAN_CONJ : 0u) |
+           (b->ran_gen ? WSR_CLASS_RAN_GEN : 0u);
+  return WSR_OK;
+}
+
 int wsr_debug_dense_lookup(const char* dir, uint32_t doc_lo, uint32_t doc_hi, uint32_t dense_div,
                            const char* term, const uint32_t* docs, int32_t n, int32_t* tf_out,
                            int32_t* is_dense) {

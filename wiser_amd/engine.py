@@ -350,6 +350,14 @@ class ResidentBatch:
         check(lib.wsr_batch_or_stats_get(self.engine._h, self._b, C.byref(st)))
         return st
 
+    def launch_class(self) -> Dict[str, bool]:
+        """wsr_debug_batch_class: the class flags of the last upload (they pick
+        the kernel instances a run launches) and ran_conj / ran_gen of the last
+        run, by name (_capi.CLASS_BITS).  Host state only."""
+        f = C.c_uint32()
+        check(lib.wsr_debug_batch_class(self.engine._h, self._b, C.byref(f)))
+        return {name: bool(f.value & bit) for name, bit in _capi.CLASS_BITS.items()}
+
     def set_item_blocks(self, blocks: int) -> None:
         """wsr_batch_set_item_blocks (disjunctive queries: before the upload)."""
         check(lib.wsr_batch_set_item_blocks(self.engine._h, self._b, blocks))
