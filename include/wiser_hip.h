@@ -178,6 +178,7 @@ typedef struct wsr_image_info {
   uint64_t dir_bytes;     /* list heads, block directory, decoded tails, doc lengths */
   uint64_t pos_bytes;     /* position boxes (positions = 1) */
   uint32_t n_lists, dense_lists;
+  uint64_t impact_bytes;  /* per-posting impact bytes (a part of dir_bytes) */
 } wsr_image_info;
 
 const char* wsr_last_error(void);
@@ -202,6 +203,13 @@ int wsr_n_docs(wsr_handle* h, int32_t* out);
 int wsr_lookup(wsr_handle* h, const char* term, int32_t* list_id, int32_t* doc_freq);
 /* bytes of docid+tf span held in HBM for a list (0 if absent from this shard) */
 int wsr_list_bytes(wsr_handle* h, int32_t list_id, uint64_t* out);
+/* The impact byte the loader stores for a posting of term frequency tf in a
+ * doc of length code c4 (0..255) at average doc length avg, and the value the
+ * kernels read it as: *value >= tf / (tf + cache_[c4]), the BM25 tf part
+ * without 2.2 * idf (DESIGN.md §4 "Pre-probe pruning").  tf is read as the
+ * format's i32, as the scoring does (a tf of 2^31 or more is no valid
+ * posting).  No engine needed. */
+int wsr_impact_byte(double avg, uint32_t tf, uint32_t c4, uint32_t* byte, double* value);
 
 /* The per-query checks wsr_batch_upload applies (term / k limits, flags, a
  * phrase query needs positions): WSR_OK or the code upload would return. */

@@ -68,7 +68,8 @@ class OrStats(C.Structure):
 class ImageInfo(C.Structure):
     _fields_ = [("total_bytes", C.c_uint64), ("blob_bytes", C.c_uint64), ("dense_bytes", C.c_uint64),
                 ("tf8_bytes", C.c_uint64), ("plen_bytes", C.c_uint64), ("dir_bytes", C.c_uint64),
-                ("pos_bytes", C.c_uint64), ("n_lists", C.c_uint32), ("dense_lists", C.c_uint32)]
+                ("pos_bytes", C.c_uint64), ("n_lists", C.c_uint32), ("dense_lists", C.c_uint32),
+                ("impact_bytes", C.c_uint64)]
 
 
 class ServeStats(C.Structure):
@@ -115,6 +116,8 @@ _sigs = {
     "wsr_n_docs": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "wsr_lookup": (C.c_int, [_P, C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "wsr_list_bytes": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_uint64)]),
+    "wsr_impact_byte": (C.c_int, [C.c_double, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
+                                  C.POINTER(C.c_double)]),
     "wsr_search_batch": (C.c_int, [_P, C.POINTER(Query), C.c_int32, C.c_int32, C.POINTER(Hit),
                                    C.POINTER(C.c_int32)]),
     "wsr_check_query": (C.c_int, [_P, C.POINTER(Query)]),

@@ -10,6 +10,7 @@
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <cstdlib>
@@ -24,6 +25,7 @@
 #include "../../include/wiser_hip.h"
 #include "dev_mem.h"
 #include "engine_types.h"
+#include "format.h"
 #include "index.h"
 #include "kernels.h"
 #include "snippet.h"
@@ -98,7 +100,7 @@ struct wsr_handle {
   gpu::DevBuf<DenseEnt> d_dense;
   gpu::DevBuf<uint32_t> d_dense_rk;   // the bitmap entries' rank records
   gpu::DevBuf<uint32_t> d_bkt;        // offset buckets (entries and offset bytes)
-  gpu::DevBuf<uint8_t> d_tf8, d_plen;
+  gpu::DevBuf<uint8_t> d_tf8, d_plen, d_impact;
   gpu::DevBuf<float> d_bmax;
   gpu::DevBuf<uint32_t> d_tails;
   gpu::DevBuf<uint8_t> d_pos_blob;    // positions (opened with wsr_open_opts::positions)
@@ -245,6 +247,8 @@ wsr_image_info image_info_of(const HostImage& img, size_t n_c4) {
   o.plen_bytes = dev_bytes(img.plen);
   o.dir_bytes = dev_bytes(img.tails) + dev_bytes(img.lists) + dev_bytes(img.blocks) + dev_bytes(img.blk_last) +
                 dev_bytes(img.blk_meta) + dev_bytes(img.bmax) + std::max<uint64_t>(n_c4, 1);
+  o.impact_bytes = dev_bytes(img.impact);   // (a part of dir_bytes)
+  o.dir_bytes += o.impact_bytes;
   o.dense_lists = img.dense_lists;
   o.n_lists = static_cast<uint32_t>(img.lists.size());
   o.total_bytes = o.blob_bytes + o.dense_bytes + o.tf8_bytes + o.plen_bytes + o.dir_bytes + o.pos_bytes;
@@ -380,6 +384,14 @@ int wsr_open(const char* dir, const wsr_open_opts* opts, wsr_handle** out) {
     h->info.blob_bytes = dev_upload(h->d_blob, img.blob);
     h->info.plen_bytes = dev_upload(h->d_plen, img.plen);
     h->args.plen = h->d_plen.get();
+    h->info.impact_bytes = dev_upload(h->d_impact, img.impact);
+    h->info.dir_bytes += h->info.impact_bytes;
+    h->args.impact = h->d_impact.get();
+    {   // (rounded down: the other terms' bound falls as the norm grows)
+      float nm = static_cast<float>(img.norm_min);
+      if (static_cast<double>(nm) > img.norm_min) nm = std::nextafter(nm, 0.0f);
+      h->args.norm_min = nm;
+    }
     h->info.dir_bytes += dev_upload(h->d_bmax, img.bmax);
     h->args.bmax = h->d_bmax.get();
     h->info.dir_bytes += dev_upload(h->d_tails, img.tails);
@@ -639,6 +651,13 @@ int wsr_highlight(const int32_t* pairs, const int32_t* counts, int32_t n_terms, 
 int wsr_list_bytes(wsr_handle* h, int32_t id, uint64_t* out) {
   if (!h || !out) return fail(WSR_E_INVALID, "null argument");
   *out = (id >= 0 && id < static_cast<int32_t>(h->list_bytes.size())) ? h->list_bytes[id] : 0;
+  return WSR_OK;
+}
+
+int wsr_impact_byte(double avg, uint32_t tf, uint32_t c4, uint32_t* byte, double* value) {
+  if (!byte || !value || c4 > 255 || !(avg > 0.0)) return fail(WSR_E_INVALID, "bad impact arguments");
+  *byte = impact_byte(tf, bm25_norm(static_cast<uint8_t>(c4), avg));
+  *value = impact_value(*byte);
   return WSR_OK;
 }
 

@@ -35,6 +35,26 @@ constexpr uint64_t kNoTail = ~0ull;
 constexpr uint64_t kNoDense = ~0ull;
 constexpr uint8_t kTf8Escape = 255;   // tf >= 255: read the tf blob instead
 
+// Impact byte of a posting (HostImage::impact): q with q * kImpactScale >=
+// tf / (tf + cache_[c4]), the tf part of its BM25 term without the 2.2 * idf
+// factor.  The scale is the f32 just above 1/255, so 255 dequantises to >= 1,
+// above every exact value (norms are > 0), and the lean pipeline bounds a
+// driver posting's own term by b_id * kImpactScale * q with one byte-to-float
+// conversion and one fma.
+constexpr float kImpactScale = 0x1.010102p-8f;
+inline double impact_value(uint32_t q) { return static_cast<double>(static_cast<float>(q) * kImpactScale); }
+// the byte the loader stores for a posting of term frequency tf in a doc of
+// length norm nrm (the real tf, also where tf8 holds the escape)
+inline uint8_t impact_byte(uint32_t tf, double nrm) {
+  const double f = static_cast<double>(static_cast<int32_t>(tf));
+  const double x = f / (f + nrm);
+  if (!(x > 0.0)) return 0;
+  if (!(x < 1.0)) return 255;
+  uint32_t q = static_cast<uint32_t>(x * 255.0);   // floor; the loop rounds up
+  while (q < 255 && impact_value(q) < x) ++q;
+  return static_cast<uint8_t>(q);
+}
+
 // A list's probe structure (ListDev::bm, QueryDesc::o_bm): bits 0-55 its
 // first entry, bits 56-63 the bucket shift c (0: a rank bitmap of DenseEnt).
 //

@@ -84,6 +84,13 @@ inline uint32_t char4_to_length(uint8_t c) {
   return (mant | 0x08) << shift;  // wraps to 0 for shift >= 29, as the reference
 }
 
+// Bm25Similarity::BuildCache (scoring.h:85-90): cache_[c] of a doc-length code
+inline double bm25_norm(uint8_t c, double avg) {
+  const double k1 = 1.2, b = 0.75;
+  const uint32_t fl = char4_to_length(c);
+  return k1 * (1 - b + b * fl / avg);
+}
+
 // ------------------------------------------------------------ bit packing --
 // Serialised pack: 0xD6 | b | 16*b data bytes, b in [1, 32].
 inline int pack_bits_for(const uint32_t* v, int n) {

@@ -127,13 +127,7 @@ void VacuumIndex::open(const std::string& dir) {
     n_docs_ = count;
   }
   // Bm25Similarity::BuildCache (scoring.h:85-90): k1 * (1 - b + b * len / avg)
-  {
-    const double k1 = 1.2, b = 0.75;
-    for (int i = 0; i < 256; ++i) {
-      const uint32_t fl = char4_to_length(static_cast<uint8_t>(i));
-      cache_[i] = k1 * (1 - b + b * fl / avg_);
-    }
-  }
+  for (int i = 0; i < 256; ++i) cache_[i] = bm25_norm(static_cast<uint8_t>(i), avg_);
   // --- my.vacuum
   {
     int fd = ::open((dir + "/my.vacuum").c_str(), O_RDONLY);
@@ -378,6 +372,7 @@ HostImage build_image(const VacuumIndex& idx, uint32_t doc_lo, uint32_t doc_hi, 
   struct Scratch {   // per worker thread, reused from list to list
     std::vector<SkipRow> rows;
     std::vector<uint32_t> last, docs, tfs;
+    bool code_used[256] = {false};   // doc-length codes of the image's postings (pass 3)
   };
   if (threads < 1) threads = 1;
   std::vector<Scratch> scratch(threads);
@@ -491,14 +486,14 @@ HostImage build_image(const VacuumIndex& idx, uint32_t doc_lo, uint32_t doc_hi, 
 
   lap("pass 1 (sizes)");
   if (hbm_free) {
-    // the rest of the image: blob, directory, plen and bmax (156 B per block),
+    // the rest of the image: blob, directory, plen, impact and bmax (284 B per block),
     // decoded tails, blooms (positions are not sized yet: the 10 % margin)
     uint64_t other = static_cast<uint64_t>(std::max(idx.n_docs(), 0));
     for (int32_t id = 0; id < L; ++id) {
       const Info& in = info[id];
       if (in.r1 <= in.r0) continue;
       const uint64_t nbl = in.r1 - in.r0;
-      other += in.bytes + nbl * (sizeof(BlockDev) + 12 + kPackSize) + (in.vtail ? 8ull * in.tail_cnt : 0);
+      other += in.bytes + nbl * (sizeof(BlockDev) + 12 + 2 * kPackSize) + (in.vtail ? 8ull * in.tail_cnt : 0);
       if (blooms && positions) other += nbl * kPackSize * 32;
     }
     const uint64_t cap = hbm_free / 10 * 9;
@@ -576,6 +571,7 @@ HostImage build_image(const VacuumIndex& idx, uint32_t doc_lo, uint32_t doc_hi, 
   img.blk_last.resize(nb);
   img.blk_meta.resize(nb);
   img.plen.resize(nb * kPackSize);
+  img.impact.resize(nb * kPackSize);
   img.bmax.resize(nb);
   img.tails.resize(ntail);
   img.dense.resize(ne);
@@ -670,6 +666,13 @@ HostImage build_image(const VacuumIndex& idx, uint32_t doc_lo, uint32_t doc_hi, 
         const double t = (f * (1.2 + 1)) / (f + norm[o[i]]);
         bm = t > bm ? t : bm;
       }
+      // every posting's impact byte (the real tf, whatever tf8 holds for it)
+      uint8_t* im = &img.impact[j * kPackSize];
+      for (int i = 0; i < cnt; ++i) {
+        im[i] = impact_byte(tfs[i], norm[o[i]]);
+        s.code_used[o[i]] = true;
+      }
+      for (int i = cnt; i < kPackSize; ++i) im[i] = 0;
       float bmf = static_cast<float>(bm);
       if (static_cast<double>(bmf) < bm) bmf = std::nextafter(bmf, std::numeric_limits<float>::infinity());
       img.bmax[j] = bmf;
@@ -861,6 +864,21 @@ HostImage build_image(const VacuumIndex& idx, uint32_t doc_lo, uint32_t doc_hi, 
   });
 
   lap("pass 3 (fill)");
+  // the smallest norm among the image's postings (an empty image: cache_'s)
+  {
+    bool any = false;
+    double nm = 0.0;
+    for (int c = 0; c < 256; ++c) {
+      bool used = false;
+      for (const Scratch& s : scratch) used = used || s.code_used[c];
+      if (used && (!any || norm[c] < nm)) { nm = norm[c]; any = true; }
+    }
+    if (!any) {
+      nm = norm[0];
+      for (int c = 1; c < 256; ++c) nm = std::min(nm, norm[c]);
+    }
+    img.norm_min = nm;
+  }
   if (positions) {
     uint64_t pb = 0;
     for (auto& p : pos_parts) pb += (p.bytes.size() + 15) & ~15ull;

@@ -138,6 +138,10 @@ struct HostImage {
   big_vector<float> bmax;       // per block: the largest TfNormLossy (tf * 2.2) / (tf + cache_[c4])
                                 // of its postings (scoring.h:65-69), f32 rounded up: idf times it
                                 // bounds every score of the block (single-term block skipping)
+  big_vector<uint8_t> impact;   // per posting, laid out as plen: impact_byte(tf, cache_[c4]), an
+                                // upper bound of tf / (tf + cache_[c4]) in 1/255 steps, 0 past a
+                                // block's postings (the lean pipeline's pre-probe pruning)
+  double norm_min = 0.0;        // the smallest cache_[c4] over the image's postings
   // positions (build_image(..., positions = true)): see PosDev
   bool has_positions = false;
   std::vector<uint8_t> pos_blob;

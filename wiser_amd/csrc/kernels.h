@@ -32,6 +32,9 @@ struct IndexArgs {
                             // wsr_batch_set_item_blocks: a latency-bound caller takes shorter items)
   const uint8_t* plen;      // doc-length code of each posting, 128 per block (HostImage::plen)
   const float* bmax;        // per block: its largest TfNormLossy, f32 rounded up (HostImage::bmax)
+  const uint8_t* impact;    // impact byte of each posting, 128 per block as plen (HostImage::impact)
+  float norm_min;           // the smallest doc-length norm of the image's postings, f32 rounded down
+                            // (HostImage::norm_min): the lean pipeline bounds the other terms there
   const uint32_t* tails;    // decoded VInts last blocks (ListDev::tail)
   // positions (phrase queries; null unless the engine was opened with them)
   const uint8_t* pos_blob;  // every list's position cozy box, byte-exact from my.vacuum

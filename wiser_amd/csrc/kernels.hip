@@ -1844,14 +1844,17 @@ __device__ __forceinline__ void pair_values(uint32_t w0, uint32_t w1, uint32_t w
 // through a software pipeline, one block per stage and iteration j:
 //   C(j-2)  compaction: the survivors of block j-2 (docs present in the most
 //           selective other list O1) are appended, in doc order, to a queue in
-//           LDS with their doc-length code and both tfs; every full 64 are
-//           scored one per lane (all query terms, query order, the further
-//           other lists probed here) and fed to the running top-k;
+//           LDS with their driver posting slot and O1's tf; every full 64 are
+//           scored one per lane (the survivor's exact driver tf and doc-length
+//           code are read here, by its slot; all query terms, query order, the
+//           further other lists probed) and fed to the running top-k;
 //   H(j-1)  O1's bitmap words of block j-1 give hits and posting ranks; the
 //           hits' 1-byte tfs are loaded;
-//   D(j)    block j's doc ids are unpacked and prefix-summed; O1's bitmap
-//           words, the doc-length bytes and the driver's tf words are loaded;
-//   W(j+1)  the doc-id pack words of block j+1 (and the score floor) are loaded.
+//   D(j)    block j's doc ids are unpacked and prefix-summed; each posting's
+//           score bound is taken from its impact byte (IndexArgs::impact:
+//           neither its tf nor its length code is decoded) and O1's bitmap
+//           words of the postings that pass are loaded;
+//   W(j+1)  the doc-id pack words and the impact bytes of block j+1 are loaded.
 // Every load is issued unconditionally (drained stages read index 0) so each
 // stage waits only for loads issued one iteration earlier.  Scoring one
 // survivor per lane instead of two postings per lane keeps the f64 work
@@ -1875,10 +1878,10 @@ constexpr int kLeanDeep = 0;
 // profiles/r03_knob_ab.txt).
 constexpr uint32_t kLeanEvs = 64;
 // LDS of one wave of the lean kernel (kPh: phrase instance, whose queue also
-// carries the driver's posting slot and O1's posting rank of every survivor)
+// carries O1's posting rank of every survivor)
 template <bool kPh>
 struct LeanLdsT {
-  uint32_t q[kPh ? 1536 : 1024];   // survivor queue (4 or 6 rings of 256); at item end the
+  uint32_t q[kPh ? 1536 : 1024];   // survivor queue (rings of 256 at fixed offsets); at item end the
                                    // replay's segment scan
   Event evs[kLeanEvs];   // events buffered in LDS, stored when a chunk could overflow them
                          // and at the end
@@ -1942,12 +1945,20 @@ __device__ __forceinline__ void lean_segment(const IndexArgs& ix, LeanLdsT<kPh>&
   const uint32_t lo = in_vgpr(ix.doc_lo), span = in_vgpr(ix.dense_span);
   const uint32_t hi_rel = in_vgpr(ix.doc_hi - ix.doc_lo);   // docs a with a - lo < hi_rel are in the image
   const double idf_d = in_vgpr(Q.a_idf), idf_o = in_vgpr(Q.o_idf);
+  // kImp: D prunes on impact bytes and a survivor's exact driver tf and
+  // length code are read by its posting slot when it is scored (the
+  // conjunctive instances).  The phrase instances decode both in D and carry
+  // them in the queue: a phrase item scores a larger share of its postings,
+  // and the slot's dependent loads in front of every chunk cost its leg 3 %
+  // (DESIGN.md 5.0000).
+  constexpr bool kImp = !kPh;
   uint32_t* qdoc = S.q;             // survivor queue (ring of 256)
-  uint32_t* qc4 = qdoc + 256;
-  uint32_t* qtd = qdoc + 512;
+  uint32_t* qc4 = qdoc + 256;       // (!kImp) doc-length code
+  uint32_t* qtd = qdoc + 512;       // (!kImp) driver tf
   uint32_t* qto = qdoc + 768;       // tf byte, or 0x80000000 | posting index when escaped
-  uint32_t* qpd = qdoc + (kPh ? 1024 : 0);   // phrase: driver posting slot
-  uint32_t* qpo = qdoc + (kPh ? 1280 : 0);   //         O1 posting rank
+  // driver posting slot in the image (block * 128 + posting): kImp, and the phrase check
+  uint32_t* qpd = qdoc + (kPh ? 1024 : 256);
+  uint32_t* qpo = qdoc + (kPh ? 1280 : 0);   // phrase: O1 posting rank
   const uint32_t o_slot0 = (kPh && phrase) ? ix.lists[Q.o_list].blk0 * 128u : 0u;
   uint32_t qhead = 0, qtail = 0;
   uint32_t bend = b1;
@@ -1967,26 +1978,39 @@ __device__ __forceinline__ void lean_segment(const IndexArgs& ix, LeanLdsT<kPh>&
   // next iteration waits for anyway, and consumed one refresh later.
   uint64_t floor_next = 0;   // per lane: one earlier item's pub
   double sent = 0.0;
-  // Pre-probe pruning.  A driver posting whose score bound -- its own term,
-  // exact, plus QueryDesc's bound of the other terms at its doc length -- is
-  // <= the threshold known so far, max(the floor of the query's earlier items,
-  // the running k-th best), can be no event: the reference heap inserts only a
-  // strictly larger score (query_processing.h:595-602), and both only grow.
-  // Such a posting is dropped before its bitmap probe.  The bound is f32 and
-  // the threshold carries a 0.2 % margin, far above the bound's rounding, so a
-  // dropped posting's f64 score is strictly below the threshold.
+  // Pre-probe pruning.  A driver posting whose score bound -- its own term
+  // from its impact byte, which dequantises to no less than tf / (tf + norm),
+  // plus QueryDesc's bound of the other terms at the image's smallest norm,
+  // where it is largest -- is <= the threshold known so far, max(the floor of
+  // the query's earlier items, the running k-th best), can be no event: the
+  // reference heap inserts only a strictly larger score
+  // (query_processing.h:595-602), and both only grow.  Such a posting is
+  // dropped before its bitmap probe, with neither its tf nor its length code
+  // decoded.  The bound is f32 and the threshold carries a 0.2 % margin, far
+  // above the bound's rounding, so a dropped posting's f64 score is strictly
+  // below the threshold.
   constexpr float kPruneMargin = 0.998f;
-  const float b_id = Q.b_id;
-  float b_iom = Q.b_iom, b_m = Q.b_m;
+  const float b_idq = Q.b_id * kImpactScale;
+  const float b_ob = Q.b_iom * __builtin_amdgcn_rcpf(Q.b_m + ix.norm_min);
   float thr_s = wide ? -1.0f
                      : static_cast<float>(__longlong_as_double(static_cast<long long>(
                            (static_cast<uint64_t>(uni(static_cast<uint32_t>(floor_bits >> 32))) << 32) |
                            uni(static_cast<uint32_t>(floor_bits))))) * kPruneMargin;
-  auto bound = [&](uint32_t t, uint32_t c) __attribute__((always_inline)) {
+  auto bound = [&](uint32_t q) __attribute__((always_inline)) {
+    return __builtin_fmaf(b_idq, static_cast<float>(q), b_ob);
+  };
+  // (!kImp: the posting's own tf and length code, both parts exact in them)
+  const float b_id = Q.b_id, b_iom = Q.b_iom, b_m = Q.b_m;
+  auto bound_tc = [&](uint32_t t, uint32_t c) __attribute__((always_inline)) {
     const float nf = static_cast<float>(norm_tab[c]);
     const float f = static_cast<float>(t);
     return b_id * f * __builtin_amdgcn_rcpf(f + nf) + b_iom * __builtin_amdgcn_rcpf(b_m + nf);
   };
+  // The exact driver tf and length code of a survivor, by its posting slot
+  // (score_chunk): the code from plen, the tf from the block's tf pack (two
+  // aligned dwords cover a value of up to 32 bits at any bit offset), or from
+  // the decoded VInts tail, which lanes 0..63 hold two postings each.
+  const uint32_t a_slot0 = Q.a_blk0 * 128u;
 
   auto flush = [&]() __attribute__((always_inline)) {
     __builtin_amdgcn_wave_barrier();
@@ -2000,12 +2024,35 @@ __device__ __forceinline__ void lean_segment(const IndexArgs& ix, LeanLdsT<kPh>&
     const uint32_t e = (qhead + l) & 255u;
     bool alive = l < n;
     const uint32_t doc = qdoc[e];
-    const uint32_t c4 = qc4[e];
-    const uint32_t td = qtd[e];
+    // (a lane past the chunk holds a stale entry: it reads the segment's first slot)
+    const uint32_t pd = (!kImp || alive) ? qpd[e] : a_slot0 + b0 * 128u;
     uint32_t to = qto[e];
-    const uint32_t pd = kPh ? qpd[e] : 0u, po = kPh ? qpo[e] : 0u;
+    const uint32_t po = kPh ? qpo[e] : 0u;
+    // the slot's block in the segment's directory (!kImp: unused, entry 0)
+    const uint32_t pbi = kImp ? (pd - a_slot0) / 128u - b0 : 0u;
+    const uint32_t ptb = S.dmeta[pbi] >> 8;            // its tf pack width (0: the VInts tail)
+    const uint32_t ptw = S.dblk[pbi].w;
+    uint32_t c4 = kImp ? 0u : (qc4[e] & 255u), td = kImp ? 0u : qtd[e];
     __builtin_amdgcn_wave_barrier();
     qhead += n;
+    if constexpr (kImp) {
+      uint32_t csh;
+      const uint32_t cw = byte_word(ix.plen + pd, &csh);
+      const uint32_t tb = ptb ? ptb : 1u;
+      const uint32_t bit = (pd & 127u) * tb;
+      const uint8_t* ta = a_blob + ptw + 2 + (bit >> 3);
+      const uint32_t tsh = (static_cast<uint32_t>(reinterpret_cast<uintptr_t>(ta) & 3) << 3) + (bit & 7u);
+      const uint32_t* tw = reinterpret_cast<const uint32_t*>(__builtin_align_down(ta, 4));
+      const uint32_t t0 = tw[0], t1 = tw[1];
+      // (the tail's tfs: posting p is lane p / 2's ttf0 or ttf1)
+      const int tl4 = static_cast<int>((pd & 126u) << 1);   // (byte index of lane p / 2)
+      const uint32_t v0 = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(tl4, static_cast<int>(ttf0)));
+      const uint32_t v1 = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(tl4, static_cast<int>(ttf1)));
+      c4 = (cw >> csh) & 0xFFu;
+      const uint64_t both = (static_cast<uint64_t>(t1) << 32) | t0;
+      td = static_cast<uint32_t>(both >> tsh) & (tb >= 32 ? 0xFFFFFFFFu : ((1u << tb) - 1u));
+      if (ptb == 0) td = (pd & 1u) ? v1 : v0;
+    }
     if (__ballot(alive && (to & 0x80000000u))) {   // O1's tf bytes by rank (bit 31: a rank)
       const bool rk = alive && (to & 0x80000000u);
       uint32_t t = load_byte(o_tf8 + (rk ? (to & 0x7FFFFFFFu) : 0u));
@@ -2015,7 +2062,7 @@ __device__ __forceinline__ void lean_segment(const IndexArgs& ix, LeanLdsT<kPh>&
       }
       if (rk) to = t;
     }
-    const double norm = norm_tab[c4 & 255u];
+    const double norm = norm_tab[c4];
     double sc = 0.0;   // BM25 accumulated in query-term order (scoring.h:133-144)
     if constexpr (kTwo) {   // the two terms in query order: the driver's slot first or second
       const double sd = bm25_term(idf_d, alive ? td : 0u, norm), so = bm25_term(idf_o, alive ? to : 0u, norm);
@@ -2120,17 +2167,19 @@ __device__ __forceinline__ void lean_segment(const IndexArgs& ix, LeanLdsT<kPh>&
     // directory in LDS where they are used, so that no scalar registers hold
     // them across the iteration)
     uint32_t w0 = 0, w1 = 0, w2 = 0;               // doc-id pack words of the next block
-    uint32_t wc = 0;                               //   its doc-length codes (2 bytes of a word)
-    uint32_t wt0 = 0, wt1 = 0, wt2 = 0;            //   its driver tf pack words
+    uint32_t wi = 0;                               //   its impact bytes (postings 2l, 2l + 1)
+    uint32_t wc = 0;                               //   (!kImp) its doc-length codes (2 bytes of a word)
+    uint32_t wt0 = 0, wt1 = 0, wt2 = 0;            //   (!kImp) its driver tf pack words
     // D: a decoded block and its loads in flight
-    uint32_t da0 = ~0u, da1 = ~0u, dcc = 0;        // docs, doc-length codes (c0 | c1 << 8)
-    uint32_t dt0 = 0, dt1 = 0;                     // driver tfs
+    uint32_t da0 = ~0u, da1 = ~0u;                 // docs
+    uint32_t dcc = 0, dt0 = 0, dt1 = 0;            // (!kImp) doc-length codes (c0 | c1 << 8), driver tfs
     std::conditional_t<kBk, uint2, uint32_t> de0{}, de1{};   // O1 bitmap mask words / bucket entries
     // (per-lane flags ride in the values -- a doc of ~0u is a posting past the
     // block, outside the image or pruned, a rank with bit 31 set is an O1 miss
     // -- so that they take no scalar lane-mask registers across the iteration)
     // H: the block decoded one iteration earlier, with its O1 hits
-    uint32_t ha0 = 0, ha1 = 0, hc0 = 0, hc1 = 0, ht0 = 0, ht1 = 0;   // docs, length codes, driver tfs
+    uint32_t ha0 = 0, ha1 = 0;                     // docs
+    uint32_t hc0 = 0, hc1 = 0, ht0 = 0, ht1 = 0;   // (!kImp) length codes, driver tfs
     uint2 hf0 = make_uint2(0, 0), hf1 = make_uint2(0, 0);   // O1 rank records (rank, 4 tfs; in flight)
                                                             // kBk: the hit's tf word, the bucket count
     uint32_t hx0 = 0x80000000u, hx1 = 0x80000000u; // O1 posting ranks (bit 31: no hit; kBk: bit 30,
@@ -2153,10 +2202,15 @@ __device__ __forceinline__ void lean_segment(const IndexArgs& ix, LeanLdsT<kPh>&
     // (VInts tail: width 0 -> a harmless dummy read)
     uint32_t sh;
     pair_words(a_blob + uni(e.z) + 2, (m & 0xFF) ? (m & 0xFF) : 1u, l, Y.w0, Y.w1, Y.w2, sh);
-    // its doc-length codes (postings 2l, 2l+1: one line per block, plen) and
-    // driver tfs, so that D can bound each posting's score before the probe
-    Y.wc = reinterpret_cast<const uint32_t*>(ix.plen)[(Q.a_blk0 + (b < b1 ? b : b0)) * 32u + (l >> 1)];
-    pair_words(a_blob + uni(e.w) + 2, (m >> 8) ? (m >> 8) : 1u, l, Y.wt0, Y.wt1, Y.wt2, sh);
+    // its impact bytes (postings 2l, 2l+1: one line per block), so that D can
+    // bound each posting's score before the probe (!kImp: its doc-length
+    // codes, one line per block, and driver tf words)
+    if constexpr (kImp) {
+      Y.wi = reinterpret_cast<const uint16_t*>(ix.impact)[(Q.a_blk0 + (b < b1 ? b : b0)) * 64u + l];
+    } else {
+      Y.wc = reinterpret_cast<const uint32_t*>(ix.plen)[(Q.a_blk0 + (b < b1 ? b : b0)) * 32u + (l >> 1)];
+      pair_words(a_blob + uni(e.w) + 2, (m >> 8) ? (m >> 8) : 1u, l, Y.wt0, Y.wt1, Y.wt2, sh);
+    }
   };
   auto stage_C = [&](Regs& X, Regs& Y, uint32_t j) __attribute__((always_inline)) {
     // C(j-2-kDeep): compaction of that block (its H fields are in X)
@@ -2207,12 +2261,17 @@ __device__ __forceinline__ void lean_segment(const IndexArgs& ix, LeanLdsT<kPh>&
       // most 63 + 128 entries are live, so it is never one of them)
       const uint32_t spare = (qhead - 1u) & 255u;
       const uint32_t e0 = hh0 ? (r0 & 255u) : spare, e1 = hh1 ? (r1 & 255u) : spare;
-      qdoc[e0] = X.ha0; qc4[e0] = X.hc0; qtd[e0] = X.ht0; qto[e0] = to0;
-      qdoc[e1] = X.ha1; qc4[e1] = X.hc1; qtd[e1] = X.ht1; qto[e1] = to1;
-      if (kPh) {   // block j-2's postings 2l, 2l+1 and their O1 ranks
-        const uint32_t pd0 = (Q.a_blk0 + j - 2 - kDeep) * 128u + 2 * l;
-        qpd[e0] = pd0; qpo[e0] = rk0;
-        qpd[e1] = pd0 + 1; qpo[e1] = rk1;
+      // (block j-2's postings 2l, 2l+1)
+      const uint32_t pd0 = a_slot0 + (j - 2 - kDeep) * 128u + 2 * l;
+      qdoc[e0] = X.ha0; qpd[e0] = pd0; qto[e0] = to0;
+      qdoc[e1] = X.ha1; qpd[e1] = pd0 + 1; qto[e1] = to1;
+      if (kPh) {   // their O1 ranks
+        qpo[e0] = rk0;
+        qpo[e1] = rk1;
+      }
+      if (!kImp) {
+        qc4[e0] = X.hc0; qtd[e0] = X.ht0;
+        qc4[e1] = X.hc1; qtd[e1] = X.ht1;
       }
       qtail += __popcll(m0) + __popcll(m1);
       // (at most two full chunks: fewer than 64 + 128 entries are queued;
@@ -2249,10 +2308,12 @@ __device__ __forceinline__ void lean_segment(const IndexArgs& ix, LeanLdsT<kPh>&
       Y.hx0 = h0 ? k0 : sc0 ? (0x40000000u | (n0 << 23) | r0) : 0x80000000u;
       Y.hx1 = h1 ? k1 : sc1 ? (0x40000000u | (n1 << 23) | r1) : 0x80000000u;
       Y.ha0 = X.da0; Y.ha1 = X.da1;
-      Y.hc0 = X.dcc & 0xFFu;
-      Y.hc1 = X.dcc >> 8;
-      Y.ht0 = X.dt0;
-      Y.ht1 = X.dt1;
+      if (!kImp) {
+        Y.hc0 = X.dcc & 0xFFu;
+        Y.hc1 = X.dcc >> 8;
+        Y.ht0 = X.dt0;
+        Y.ht1 = X.dt1;
+      }
     } else {
       const uint32_t q0 = X.da0 - lo, q1 = X.da1 - lo;
       const uint32_t s0 = q0 % kDenseDocs, s1 = q1 % kDenseDocs;
@@ -2270,10 +2331,12 @@ __device__ __forceinline__ void lean_segment(const IndexArgs& ix, LeanLdsT<kPh>&
       Y.hx1 = h1 ? (x1 & 0x7FFFFFFFu) : 0x80000000u;
 
       Y.ha0 = X.da0; Y.ha1 = X.da1;
-      Y.hc0 = X.dcc & 0xFFu;
-      Y.hc1 = X.dcc >> 8;
-      Y.ht0 = X.dt0;
-      Y.ht1 = X.dt1;
+      if (!kImp) {
+        Y.hc0 = X.dcc & 0xFFu;
+        Y.hc1 = X.dcc >> 8;
+        Y.ht0 = X.dt0;
+        Y.ht1 = X.dt1;
+      }
     }
   };
   auto stage_D = [&](Regs& X, Regs& Yd, uint32_t j) __attribute__((always_inline)) {
@@ -2288,7 +2351,7 @@ __device__ __forceinline__ void lean_segment(const IndexArgs& ix, LeanLdsT<kPh>&
       const uint4 be = S.dblk[bi];
       const uint32_t m = uni(S.dmeta[bi]);
       const uint32_t prev = uni(be.x);
-      const uint32_t wbits = (m & 0xFF) ? (m & 0xFF) : 1u, wtb = (m >> 8) ? (m >> 8) : 1u;
+      const uint32_t wbits = (m & 0xFF) ? (m & 0xFF) : 1u;
       const uint32_t cnt = live ? ((j == Q.a_nblk - 1) ? Q.a_tail_cnt : 128u) : 0u;
       uint32_t x0, x1;
       pair_values(X.w0, X.w1, X.w2, pair_shift(uni(be.z), wbits), wbits, x0, x1);
@@ -2300,15 +2363,24 @@ __device__ __forceinline__ void lean_segment(const IndexArgs& ix, LeanLdsT<kPh>&
       if (tl) { a0 = tdoc0; a1 = tdoc1; }
       const bool ok0 = (2 * l < cnt) & (a0 - lo < hi_rel);
       const bool ok1 = (2 * l + 1 < cnt) & (a1 - lo < hi_rel);
-      uint32_t t0, t1;
-      pair_values(X.wt0, X.wt1, X.wt2, pair_shift(uni(be.w), wtb), wtb, t0, t1);
-      if (tl) { t0 = ttf0; t1 = ttf1; }
-      const uint32_t c0 = (X.wc >> ((l & 1u) << 4)) & 0xFFu;
-      const uint32_t c1 = (X.wc >> (((l & 1u) << 4) + 8)) & 0xFFu;
       // pre-probe pruning (above): a dropped posting is never probed
       // (branch-free: the bound of a lane past the block is computed and dropped)
-      const bool p0 = ok0 & (bound(t0, c0) > thr_s);
-      const bool p1 = ok1 & (bound(t1, c1) > thr_s);
+      bool p0, p1;
+      if constexpr (kImp) {
+        p0 = ok0 & (bound(X.wi & 0xFFu) > thr_s);
+        p1 = ok1 & (bound((X.wi >> 8) & 0xFFu) > thr_s);
+      } else {
+        const uint32_t wtb = (m >> 8) ? (m >> 8) : 1u;
+        uint32_t t0, t1;
+        pair_values(X.wt0, X.wt1, X.wt2, pair_shift(uni(be.w), wtb), wtb, t0, t1);
+        if (tl) { t0 = ttf0; t1 = ttf1; }
+        const uint32_t c0 = (X.wc >> ((l & 1u) << 4)) & 0xFFu;
+        const uint32_t c1 = (X.wc >> (((l & 1u) << 4) + 8)) & 0xFFu;
+        p0 = ok0 & (bound_tc(t0, c0) > thr_s);
+        p1 = ok1 & (bound_tc(t1, c1) > thr_s);
+        Y.dcc = c0 | (c1 << 8);
+        Y.dt0 = t0; Y.dt1 = t1;
+      }
       const bool in0 = p0 & (a0 - lo < span);
       const bool in1 = p1 & (a1 - lo < span);
       if constexpr (kBk) {
@@ -2318,8 +2390,6 @@ __device__ __forceinline__ void lean_segment(const IndexArgs& ix, LeanLdsT<kPh>&
         Y.de0 = o_probe(in0 ? (a0 - lo) / kDenseDocs : 0u);
         Y.de1 = o_probe(in1 ? (a1 - lo) / kDenseDocs : 0u);
       }
-      Y.dcc = c0 | (c1 << 8);
-      Y.dt0 = t0; Y.dt1 = t1;
       Y.da0 = p0 ? a0 : ~0u; Y.da1 = p1 ? a1 : ~0u;
       if (live) ++n_dblk;
       // past the smallest last doc of the other lists nothing later can match
