@@ -7,8 +7,8 @@ JOBS    ?= 8
 LIB     := wiser_amd/_lib/libwiser_hip.so
 ORACLE  := oracle/_build/liboracle.so
 SRCS    := wiser_amd/csrc/writer.cc wiser_amd/csrc/index.cc wiser_amd/csrc/engine.cc \
-           wiser_amd/csrc/server.cc wiser_amd/csrc/docstore.cc wiser_amd/csrc/snippet.cc \
-           wiser_amd/csrc/kernels.hip
+           wiser_amd/csrc/batch_plan.cc wiser_amd/csrc/server.cc wiser_amd/csrc/docstore.cc \
+           wiser_amd/csrc/snippet.cc wiser_amd/csrc/kernels.hip
 HDRS    := $(wildcard wiser_amd/csrc/*.h) include/wiser_hip.h
 OBJDIR  := wiser_amd/_lib/obj
 OBJS    := $(patsubst wiser_amd/csrc/%,$(OBJDIR)/%.o,$(SRCS))
@@ -22,10 +22,12 @@ CLI     := wiser_amd/_lib/engine_cli
 CALIB   := wiser_amd/_lib/calib_ea
 DICT    := wiser_amd/_lib/dict_check
 DEVMEM  := wiser_amd/_lib/dev_mem_check
+BPLAN   := wiser_amd/_lib/batch_plan_check
 
-# (the buffer owner's check is a test of the header alone: a tree whose tests/
-# does not hold its source still builds everything else)
-all: $(LIB) $(ORACLE) $(CLI) $(CALIB) $(DICT) $(if $(wildcard tests/cpp/dev_mem_check.cc),$(DEVMEM))
+# (the buffer owner's and the upload plan's checks are tests of those files alone:
+# a tree whose tests/ does not hold their sources still builds everything else)
+all: $(LIB) $(ORACLE) $(CLI) $(CALIB) $(DICT) $(if $(wildcard tests/cpp/dev_mem_check.cc),$(DEVMEM)) \
+     $(if $(wildcard tests/cpp/batch_plan_check.cc),$(BPLAN))
 
 # CPU check of the term dictionary (tests/test_dictionary.py)
 $(DICT): tests/cpp/dict_check.cc wiser_amd/csrc/index.h $(LIB)
@@ -35,6 +37,12 @@ $(DICT): tests/cpp/dict_check.cc wiser_amd/csrc/index.h $(LIB)
 $(DEVMEM): tests/cpp/dev_mem_check.cc wiser_amd/csrc/dev_mem.h
 	@mkdir -p wiser_amd/_lib
 	$(CXX) -O2 -std=c++17 -Wall -o $@ tests/cpp/dev_mem_check.cc
+
+# CPU check of the upload plan on a hand-made image (tests/test_batch_plan.py): no HIP, no engine
+$(BPLAN): tests/cpp/batch_plan_check.cc wiser_amd/csrc/batch_plan.cc wiser_amd/csrc/batch_plan.h \
+          wiser_amd/csrc/engine_types.h include/wiser_hip.h
+	@mkdir -p wiser_amd/_lib
+	$(CXX) -O2 -std=c++17 -Wall -o $@ tests/cpp/batch_plan_check.cc wiser_amd/csrc/batch_plan.cc
 
 # counter calibration (profiles only): known-byte reads for rocprofv3 --pmc
 $(CALIB): scripts/calib_ea.hip

@@ -1,7 +1,7 @@
 """Every lean and segment kernel instance on the edge-case corpora.
 
 wsr_batch_upload picks the kernel instances of a batch from the batch's class
-flags (engine.cc, launch_lean): the two-term and the single-term lean
+flags (plan_upload in batch_plan.cc, launch_lean): the two-term and the single-term lean
 specialisations, the plain conjunctive lean instance, the two phrase lean
 instances, the general kernel without / with a phrase and the wide replay.
 The other parity tests send mixed batches to the corpora built to break the

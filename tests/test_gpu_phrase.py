@@ -247,7 +247,7 @@ def test_bloom_pruning_follows_reference(bloom_indexes, tmp_path, factor):
 
 def test_phrase_only_batch_stats_are_its_own(positions_index):
     """A batch of phrase queries alone launches neither the conjunctive lean
-    kernel nor the general one (engine.cc batch_run); its statistics must not
+    kernel nor the general one (launches_of, batch_plan.h); its statistics must not
     read those kernels' rows, which still hold the batch's previous run."""
     import wiser_amd as w
     from wiser_amd import _capi

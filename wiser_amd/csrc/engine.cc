@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/wiser_hip.h"
+#include "batch_plan.h"
 #include "dev_mem.h"
 #include "engine_types.h"
 #include "format.h"
@@ -31,22 +32,10 @@
 #include "snippet.h"
 #include "writer.h"
 
-namespace wiser {
-constexpr int kSegCostMax = kSegCost;
-}  // namespace wiser
-
 using namespace wiser;
 
 namespace {
 thread_local std::string g_err;
-
-// the list ids of a query in query order (list_ids, then more_ids)
-std::vector<int32_t> query_terms(const wsr_query& q) {
-  std::vector<int32_t> t(q.n_terms > 0 ? static_cast<size_t>(q.n_terms) : 0u);
-  for (int i = 0; i < q.n_terms; ++i) t[i] = i < WSR_MAX_TERMS ? q.list_ids[i] : q.more_ids[i - WSR_MAX_TERMS];
-  return t;
-}
-
 
 int fail(int code, const std::string& msg) {
   g_err = msg;
@@ -125,6 +114,25 @@ struct wsr_handle {
   int lean_wgs_ph = 0; // ... its phrase instance's
   int lean_wgs_two = 0; // ... its two-term instance's (one workgroup per CU past residency)
   int gen_cap = 0;     // general workgroups launched at most
+  // what the upload plan (batch_plan.h) reads of the handle
+  ImageView view() const {
+    ImageView v;
+    v.lists = lists.data();
+    v.n_lists = lists.size();
+    v.blocks = blocks.data();
+    v.n_blocks = blocks.size();
+    v.list_bytes = list_bytes.data();
+    v.pos_bytes = pos_bytes.empty() ? nullptr : pos_bytes.data();
+    v.dense_ratio = args.dense_ratio;
+    v.doc_lo = args.doc_lo;
+    v.doc_hi = args.doc_hi;
+    v.positions = positions;
+    v.lean_wgs = lean_wgs;
+    v.lean_wgs_two = lean_wgs_two;
+    v.lean_wgs_ph = lean_wgs_ph;
+    v.gen_cap = gen_cap;
+    return v;
+  }
 };
 
 struct wsr_batch {
@@ -144,19 +152,9 @@ struct wsr_batch {
   gpu::DevBuf<uint64_t> d_pub;     // per item score floor
   gpu::DevBuf<uint32_t> d_stats;   // per general workgroup, then per lean wave: survivors, blocks
   gpu::DevBuf<uint32_t> d_ph;      // phrase scratch, gen_cap * kPhraseScratch (lazily)
-  bool has_phrase = false;       // the uploaded queries include a phrase query
-  bool gen_phrase = false;       // ... one of the general class (segment_kernel's phrase instance)
-  bool has_conj_lean = true;     // the host's class rule found a conjunctive lean query
-  bool has_gen = true;           // ... a general one
-  bool ran_conj = true, ran_gen = true;   // the last run launched them (their stats rows are its own)
-  bool has_wide = false;         // ... a query with k > kMaxK (wide_replay_kernel)
-  bool two_conj = false;         // every conjunctive query: two terms (or empty), k <= kMaxK
-  bool two_ph = false;           // every phrase query: k <= kMaxK (a lean one has two terms)
-  bool one_conj = false;         // every conjunctive query: one term (or empty)
+  BatchClass cls;                // the uploaded queries' class flags, grids and OR counts (plan_upload)
+  Launches launched;             // the persistent kernels of the last run (their stats rows are its own)
   uint32_t seg_cap = kSegCost;   // driver blocks per work item at most (wsr_batch_set_item_blocks)
-  int seg_grid = 0;
-  int lean_wgs = 0;      // the conjunctive lean instance's grid
-  int lean_wgs_ph = 0;   // the phrase instance's (batches with phrase queries)
   // doc-range shard exchange (wsr_shard_step): per owner a region of {count,
   // offset} pairs + an event slot, owner-major to send, shard-major received;
   // allocated on first use
@@ -184,14 +182,8 @@ struct wsr_batch {
   int32_t hdef_rank = 0;
   int x_world = 0, x_qpr = 0;   // ... for this world and q_per_owner
   int64_t x_slot = 0;           //     and slot (the replay half must match them)
-  uint64_t algo_static = 0;  // sum of list spans + k*12 over the uploaded queries
   // disjunctive (OR) queries: their table, items and event slots, allocated
-  // by the first upload that holds one (n_or == 0: no extra launch)
-  int n_or = 0;                  // OR queries with at least one resolved term and k > 0
-  uint32_t or_items = 0;
-  int or_nt_max = 0;             // the most resolved terms of one of them
-  bool or_narrow = false, or_wide = false;   // some k <= kMaxK / > kMaxK among them
-  bool has_or = false;           // the uploaded queries include an OR query (even an empty one)
+  // by the first upload that holds one (cls.n_or == 0: no extra launch)
   gpu::DevBuf<OrQuery> d_orq;
   gpu::DevBuf<OrItem> d_oritem;
   gpu::DevBuf<uint32_t> d_orevcnt;   // (sized together with d_oritem)
@@ -705,251 +697,53 @@ void wsr_batch_destroy(wsr_handle* h, wsr_batch* b) {
 
 int wsr_check_query(wsr_handle* h, const wsr_query* q) {
   if (!h || !q) return fail(WSR_E_INVALID, "null argument");
-  if (q->n_terms > WSR_MAX_QUERY_TERMS || q->k > WSR_MAX_K)
-    return fail(WSR_E_LIMIT, "n_terms or k over the limit");
-  if (q->flags & ~(WSR_QUERY_PHRASE | WSR_QUERY_OR)) return fail(WSR_E_INVALID, "unknown flags");
-  if ((q->flags & WSR_QUERY_OR) && (q->flags & WSR_QUERY_PHRASE))
-    return fail(WSR_E_INVALID, "a query is a phrase or a disjunction, not both");
-  if ((q->flags & WSR_QUERY_OR) && q->n_terms > WSR_MAX_OR_TERMS)
-    return fail(WSR_E_LIMIT, "a disjunctive query has at most WSR_MAX_OR_TERMS terms");
-  if (q->n_terms > WSR_MAX_TERMS && !q->more_ids)
-    return fail(WSR_E_INVALID, "a query of more than WSR_MAX_TERMS terms needs more_ids");
-  if ((q->flags & WSR_QUERY_PHRASE) && q->n_terms > WSR_MAX_PHRASE_TERMS)
-    return fail(WSR_E_LIMIT, "a phrase query has at most WSR_MAX_PHRASE_TERMS terms");
-  if ((q->flags & WSR_QUERY_PHRASE) && q->n_terms > 1 && !h->positions)
-    return fail(WSR_E_INVALID, "phrase query on an engine opened without positions");
-  return WSR_OK;
+  std::string why;
+  const int rc = check_query(h->view(), *q, &why);
+  return rc ? fail(rc, why) : WSR_OK;
 }
 
-// The plan of one disjunctive query (its resolved terms in oq->list): the
-// image's doc range cut into items at the last doc of every s-th block of the
-// query's longest list, s chosen so that an item carries about `target` blocks
-// over all its lists (doc ids spread alike over the lists' blocks), and each
-// item's event slot sized for its worst case -- every doc of its range an
-// event, or every posting of the blocks that overlap it.  Appends the items
-// and advances *ev_total.
-static void plan_or_query(const wsr_handle* h, uint32_t target, OrQuery* oq, std::vector<OrItem>* items,
-                          uint64_t* ev_total) {
-  const int nt = oq->nt;
-  // MaxScore bounds, summed in ascending (bound, slot) order
-  int by[kMaxOrTerms];
-  for (int t = 0; t < nt; ++t) by[t] = t;
-  auto ub = [&](int t) { return 2.2 * h->lists[oq->list[t]].idf; };
-  std::stable_sort(by, by + nt, [&](int a, int c) { return ub(a) < ub(c); });
-  double sum = 0.0;
-  for (int r = 0; r < nt; ++r) {
-    sum += ub(by[r]);
-    oq->ubsum[by[r]] = sum;
-  }
-  uint64_t total = 0;
-  int lg = 0;
-  uint32_t top = 0;   // one past the last doc of its lists in the image
-  for (int t = 0; t < nt; ++t) {
-    const ListDev& L = h->lists[oq->list[t]];
-    total += L.nblk;
-    if (L.nblk > h->lists[oq->list[lg]].nblk) lg = t;
-    top = std::max(top, L.last + 1);
-  }
-  const ListDev& G = h->lists[oq->list[lg]];
-  const uint32_t step = static_cast<uint32_t>(std::max<uint64_t>(1, uint64_t{target} * G.nblk / total));
-  const uint32_t img_lo = h->args.doc_lo, img_hi = std::min(h->args.doc_hi, top);
-  auto last_of = [&](const ListDev& L, uint32_t j) { return h->blocks[L.blk0 + j].last; };
-  // first block of L whose last doc is >= x (nblk: none)
-  auto first_block = [&](const ListDev& L, uint32_t x) {
-    const BlockDev* b0 = h->blocks.data() + L.blk0;
-    return static_cast<uint32_t>(
-        std::lower_bound(b0, b0 + L.nblk, x, [](const BlockDev& e, uint32_t v) { return e.last < v; }) - b0);
-  };
-  oq->item_base = static_cast<uint32_t>(items->size());
-  for (uint32_t j0 = 0; j0 < G.nblk; j0 += step) {
-    const uint32_t j1 = std::min(j0 + step, G.nblk);
-    const uint32_t lo = std::max(img_lo, j0 ? last_of(G, j0 - 1) + 1 : 0u);
-    const uint32_t hi = j1 == G.nblk ? img_hi : std::min(img_hi, last_of(G, j1 - 1) + 1);
-    if (lo >= hi) continue;
-    uint64_t blocks = 0;
-    for (int t = 0; t < nt; ++t) {
-      const ListDev& L = h->lists[oq->list[t]];
-      const uint32_t f = first_block(L, lo);
-      if (f < L.nblk) blocks += std::min(first_block(L, hi - 1), L.nblk - 1) - f + 1;
-    }
-    if (!blocks) continue;
-    OrItem it{};
-    it.oq = 0;   // (set at upload: the query's place in the table)
-    it.doc_lo = lo;
-    it.doc_hi = hi;
-    it.ev_cap = static_cast<uint32_t>(std::min<uint64_t>(hi - lo, 128 * blocks));
-    it.ev_base = *ev_total;
-    *ev_total += it.ev_cap;
-    items->push_back(it);
-  }
-  oq->n_items = static_cast<uint32_t>(items->size()) - oq->item_base;
-}
-
+// plan (batch_plan.cc: everything that depends on the queries alone), join
+// the batch's earlier work, grow the buffers and copy, commit the class
 int wsr_batch_upload(wsr_handle* h, wsr_batch* b, const wsr_query* q, int32_t nq) {
   if (!h || !b || (nq > 0 && !q) || nq < 0 || nq > b->max_q)
     return fail(WSR_E_INVALID, "bad upload arguments");
-  std::vector<OrQuery> orq;       // the disjunctive queries' table, items and event total
-  std::vector<OrItem> or_items;
-  uint64_t or_ev = 0;
-  bool has_or = false, or_narrow = false, or_wide = false;
-  int or_nt_max = 0;
   // (no handle lock: the handle's image is read-only after wsr_open and the
   // batch belongs to the caller, so threads with their own batches pipeline)
-  std::vector<QueryIn> in(nq);
-  std::vector<int32_t> ext;   // term lists of queries over kMaxTerms, after the QueryIn array
-  uint64_t ev_need = 0, items_need = 0, algo = 0;
-  // the device's class rule (plan_query_kernel), restated to size the two
-  // persistent grids: lean items run in lean_kernel, the rest in segment_kernel
-  uint64_t lean_need = 0, lean_need_ph = 0, gen_need = 0;
-  const float dense_ratio = h->args.dense_ratio;
-  bool has_phrase = false, has_wide = false, two_conj = true, two_ph = true, one_conj = true, gen_phrase = false;
-  std::vector<int32_t> ids;
-  for (int i = 0; i < nq; ++i) {
-    const wsr_query& s = q[i];
-    if (s.k > b->stride)
-      return fail(WSR_E_LIMIT, "query " + std::to_string(i) + ": k over the batch's hit stride");
-    const int qrc = wsr_check_query(h, &s);
-    if (qrc) return fail(qrc, "query " + std::to_string(i) + ": " + g_err);
-    if (s.flags & WSR_QUERY_OR) {
-      // a disjunctive query: an empty one to the conjunctive plan and kernels
-      // (neutral to the batch's class flags), planned here into its own table
-      QueryIn& d = in[i];
-      d.n_terms = 0;
-      d.k = s.k < 0 ? 0 : s.k;
-      d.flags = 0;
-      d.ext = 0;
-      for (int t = 0; t < kMaxTerms; ++t) d.list[t] = -1;
-      has_or = true;
-      // (only -1 means a missing term; n_terms <= WSR_MAX_OR_TERMS: the ids are inline)
-      for (int t = 0; t < s.n_terms; ++t)
-        if (s.list_ids[t] < -1 || s.list_ids[t] >= static_cast<int32_t>(h->lists.size()))
-          return fail(WSR_E_INVALID, "query " + std::to_string(i) + ": list id out of range");
-      if (s.k <= 0) continue;
-      OrQuery oq{};
-      oq.q = i;
-      oq.k = s.k;
-      for (int t = 0; t < s.n_terms; ++t) {
-        const int32_t id = s.list_ids[t];
-        if (id >= 0 && h->lists[id].nblk > 0) oq.list[oq.nt++] = id;   // (no blocks: none in this image)
-      }
-      if (oq.nt == 0) continue;
-      plan_or_query(h, b->seg_cap, &oq, &or_items, &or_ev);
-      for (int t = 0; t < oq.nt; ++t) algo += h->list_bytes[oq.list[t]];
-      algo += 12ull * oq.k;
-      for (uint32_t r = 0; r < oq.n_items; ++r)
-        or_items[oq.item_base + r].oq = static_cast<uint32_t>(orq.size());
-      if (oq.n_items) {
-        or_nt_max = std::max(or_nt_max, oq.nt);
-        (oq.k > kMaxK ? or_wide : or_narrow) = true;
-        orq.push_back(oq);
-      }
-      continue;
-    }
-    const bool phrase = (s.flags & WSR_QUERY_PHRASE) && s.n_terms > 1;
-    has_phrase = has_phrase || phrase;
-    has_wide = has_wide || s.k > kMaxK;
-    if (phrase) two_ph = two_ph && s.k <= kMaxK;
-    else {
-      two_conj = two_conj && s.k <= kMaxK && (s.n_terms == 2 || s.n_terms <= 0 || s.k <= 0);
-      one_conj = one_conj && (s.n_terms == 1 || s.n_terms <= 0 || s.k <= 0);
-    }
-    QueryIn& d = in[i];
-    d.n_terms = s.n_terms < 0 ? 0 : s.n_terms;
-    d.k = s.k < 0 ? 0 : s.k;
-    d.flags = phrase ? kQueryPhrase : 0;
-    d.ext = 0;
-    ids = query_terms(s);
-    for (int t = 0; t < kMaxTerms; ++t) d.list[t] = t < d.n_terms ? ids[t] : -1;
-    if (d.n_terms > kMaxTerms) {
-      d.ext = static_cast<uint32_t>((sizeof(QueryIn) * static_cast<size_t>(nq)) / sizeof(int32_t) + ext.size());
-      ext.insert(ext.end(), ids.begin(), ids.end());
-    }
-    uint32_t nbmin = 0xFFFFFFFFu;
-    bool ok = d.n_terms > 0 && d.k > 0;
-    for (int t = 0; t < d.n_terms; ++t) {
-      const int32_t id = ids[t];
-      if (id < 0 || id >= static_cast<int32_t>(h->lists.size())) { ok = false; continue; }
-      nbmin = std::min(nbmin, h->lists[id].nblk);
-    }
-    if (ok && nbmin > 0) {
-      // (a single-term item spans up to kSingleWindows items' blocks)
-      const uint64_t seg_max = d.n_terms == 1 ? std::min<uint64_t>(nbmin, uint64_t{kSegCostMax} * kSingleWindows)
-                                              : uint64_t{kSegCostMax};
-      ev_need += (static_cast<uint64_t>(nbmin) + seg_max) * 128;
-      items_need += nbmin;
-      int drv = 0;
-      for (int t = 1; t < d.n_terms; ++t)
-        if (h->lists[ids[t]].nblk < h->lists[ids[drv]].nblk) drv = t;
-      auto dense = [&](int t) {
-        const ListDev& L = h->lists[ids[t]];
-        return L.bm != kNoDense && static_cast<float>(L.nblk) >= dense_ratio * static_cast<float>(nbmin);
-      };
-      bool lean = !(phrase && d.n_terms > 2);   // (longer phrases: general class)
-      for (int t = 0; t < d.n_terms; ++t)
-        if (t != drv && !dense(t)) lean = false;
-      (lean ? (phrase ? lean_need_ph : lean_need) : gen_need) += nbmin;
-      gen_phrase = gen_phrase || (phrase && !lean);
-      // every term's docid+tf span, and for a phrase query also its
-      // position box (the bags the position check reads from)
-      for (int t = 0; t < d.n_terms; ++t) {
-        algo += h->list_bytes[ids[t]];
-        if (phrase && !h->pos_bytes.empty()) algo += h->pos_bytes[ids[t]];
-      }
-      algo += 12ull * d.k;
-    }
-  }
-  const size_t q_bytes = sizeof(QueryIn) * static_cast<size_t>(nq) + sizeof(int32_t) * ext.size();
+  UploadPlan p;
+  std::string why;
+  const int prc = plan_upload(h->view(), q, nq, b->stride, b->seg_cap, &p, &why);
+  if (prc) return fail(prc, why);
   try {
     HIP_OK(hipSetDevice(h->device));
     HIP_OK(hipStreamSynchronize(b->st));
     if (x_join(b)) HIP_OK(hipEventSynchronize(b->xev[1]));   // a shard step's exchange + replay
     // (on-demand buffers: a failure leaves the buffer empty, so the next upload allocates again)
-    b->d_events.reserve(ev_need, ev_need + ev_need / 4 + 4096);
-    if (items_need > b->d_evcnt.size() || !b->d_evcnt)
-      gpu::alloc_group(items_need + items_need / 4 + 1024, b->d_evcnt, b->d_itemq, b->d_pub);
-    if (has_phrase && !b->d_ph)   // one per general workgroup
+    b->d_events.reserve(p.ev_need, p.ev_need + p.ev_need / 4 + 4096);
+    if (p.items_need > b->d_evcnt.size() || !b->d_evcnt)
+      gpu::alloc_group(p.items_need + p.items_need / 4 + 1024, b->d_evcnt, b->d_itemq, b->d_pub);
+    if (p.cls.has_phrase && !b->d_ph)   // one per general workgroup
       b->d_ph.alloc(kPhraseScratch * static_cast<size_t>(std::max(h->gen_cap, 1)));
-    b->d_qb.reserve(q_bytes, q_bytes + q_bytes / 4);   // (the term table of long queries follows the QueryIn array)
-    if (!orq.empty()) {   // (a batch without a disjunctive query allocates nothing here)
-      if (or_items.size() > 0xFFFFFFFFull) return fail(WSR_E_LIMIT, "over 2^32 disjunctive work items");
-      b->d_orq.reserve(orq.size(), orq.size() + orq.size() / 4);
-      if (or_items.size() > b->d_oritem.size())
-        gpu::alloc_group(or_items.size() + or_items.size() / 4 + 64, b->d_oritem, b->d_orevcnt);
-      b->d_orev.reserve(or_ev, or_ev + or_ev / 4);
+    // (the term table of long queries follows the QueryIn array)
+    b->d_qb.reserve(p.q_bytes, p.q_bytes + p.q_bytes / 4);
+    if (!p.orq.empty()) {   // (a batch without a disjunctive query allocates nothing here)
+      const size_t n_or = p.orq.size(), n_items = p.or_items.size();
+      if (n_items > 0xFFFFFFFFull) return fail(WSR_E_LIMIT, "over 2^32 disjunctive work items");
+      b->d_orq.reserve(n_or, n_or + n_or / 4);
+      if (n_items > b->d_oritem.size()) gpu::alloc_group(n_items + n_items / 4 + 64, b->d_oritem, b->d_orevcnt);
+      b->d_orev.reserve(p.or_ev, p.or_ev + p.or_ev / 4);
       if (!b->d_orstat) b->d_orstat.alloc(kNumOrStats);
-      HIP_OK(hipMemcpy(b->d_orq, orq.data(), sizeof(OrQuery) * orq.size(), hipMemcpyHostToDevice));
-      HIP_OK(hipMemcpy(b->d_oritem, or_items.data(), sizeof(OrItem) * or_items.size(), hipMemcpyHostToDevice));
+      HIP_OK(hipMemcpy(b->d_orq, p.orq.data(), sizeof(OrQuery) * n_or, hipMemcpyHostToDevice));
+      HIP_OK(hipMemcpy(b->d_oritem, p.or_items.data(), sizeof(OrItem) * n_items, hipMemcpyHostToDevice));
     }
-    if (nq) HIP_OK(hipMemcpy(b->d_q(), in.data(), sizeof(QueryIn) * nq, hipMemcpyHostToDevice));
-    if (!ext.empty())
-      HIP_OK(hipMemcpy(reinterpret_cast<char*>(b->d_q()) + sizeof(QueryIn) * nq, ext.data(),
-                       sizeof(int32_t) * ext.size(), hipMemcpyHostToDevice));
+    if (nq) HIP_OK(hipMemcpy(b->d_q(), p.in.data(), sizeof(QueryIn) * nq, hipMemcpyHostToDevice));
+    if (!p.ext.empty())
+      HIP_OK(hipMemcpy(reinterpret_cast<char*>(b->d_q()) + sizeof(QueryIn) * nq, p.ext.data(),
+                       sizeof(int32_t) * p.ext.size(), hipMemcpyHostToDevice));
   } catch (const std::exception& e) {
     return fail(WSR_E_HIP, e.what());
   }
   b->nq = nq;
-  b->has_phrase = has_phrase;
-  b->has_wide = has_wide;
-  b->two_conj = two_conj;
-  b->gen_phrase = gen_phrase;
-  b->has_conj_lean = lean_need > 0;
-  b->has_gen = gen_need > 0;
-  b->two_ph = two_ph;
-  b->one_conj = one_conj && !two_conj;   // (a batch of empty queries only: the two-term instance)
-  // persistent grid: never more workgroups than work items can exist
-  // (at least one worker each: a grid also drains items the estimate missed)
-  b->seg_grid = static_cast<int>(std::max<uint64_t>(1, std::min<uint64_t>(h->gen_cap, gen_need)));
-  b->lean_wgs = static_cast<int>(std::max<uint64_t>(
-      1, std::min<uint64_t>(two_conj ? h->lean_wgs_two : h->lean_wgs, (lean_need + kLeanWaves - 1) / kLeanWaves)));
-  b->lean_wgs_ph = static_cast<int>(std::max<uint64_t>(
-      1, std::min<uint64_t>(h->lean_wgs_ph, (lean_need_ph + kLeanWaves - 1) / kLeanWaves)));
-  b->algo_static = algo;
-  b->has_or = has_or;
-  b->n_or = static_cast<int>(orq.size());
-  b->or_items = static_cast<uint32_t>(or_items.size());
-  b->or_nt_max = or_nt_max;
-  b->or_narrow = or_narrow;
-  b->or_wide = or_wide;
+  b->cls = p.cls;
   b->ran = false;
   return WSR_OK;
 }
@@ -988,7 +782,8 @@ int wsr_debug_fail_runs(int32_t n) {
 
 static int batch_run(wsr_handle* h, wsr_batch* b, const ShardEmit* se, const OwnerJob* oj) {
   if (!h || !b) return fail(WSR_E_INVALID, "null argument");
-  if (se && b->has_or) return fail(WSR_E_INVALID, "a doc-range shard step cannot run a disjunctive query");
+  const BatchClass& c = b->cls;
+  if (se && c.has_or) return fail(WSR_E_INVALID, "a doc-range shard step cannot run a disjunctive query");
   for (int32_t f = g_fail_runs.load(); f > 0;)
     if (g_fail_runs.compare_exchange_weak(f, f - 1)) return fail(WSR_E_HIP, "injected run failure");
   wsr_batch* pb = nullptr;   // (a host replay taken, below)
@@ -1024,22 +819,14 @@ static int batch_run(wsr_handle* h, wsr_batch* b, const ShardEmit* se, const Own
     HIP_OK(hipEventRecord(b->ev[0], st));
     IndexArgs pa = h->args;   // (the batch's item length)
     pa.seg_cap = b->seg_cap;
-    // A batch with phrase queries launches the conjunctive lean kernel and the
-    // general one only when the host's restatement of the class rule found
-    // such queries (an empty persistent launch waited for CU slots beside the
-    // others: 54 us on C5, profiles/r05p); the plan flags kErrClass if a class
-    // without a launch holds items.  (Shard steps launch everything: their
-    // owners read every query's emission.)
-    // (a taken owner replay rides in the conjunctive launch: it runs then
-    // even with no conjunctive lean item of its own)
-    const bool run_conj = se || oj || !b->has_phrase || b->has_conj_lean;
-    const bool run_gen = se || !b->has_phrase || b->has_gen;
-    b->ran_conj = run_conj;
-    b->ran_gen = run_gen;
+    // (which persistent kernels a batch with phrase queries launches: launches_of, batch_plan.h)
+    b->launched = launches_of(c, se != nullptr, oj != nullptr);
+    const bool run_conj = b->launched.conj, run_gen = b->launched.gen;
     HIP_OK(launch_plan(pa, b->d_q(), b->nq, b->d_plan, b->d_ctr, b->d_events.size(),
                        static_cast<uint32_t>(std::min<uint64_t>(b->d_evcnt.size(), 0xFFFFFFFFull)),
-                       run_conj ? kLeanWaves * b->lean_wgs : 0, b->has_phrase ? kLeanWaves * b->lean_wgs_ph : 0,
-                       run_gen ? b->seg_grid : 0, fr, b->d_itemq, b->d_pub, b->d_desc, b->d_part, st));
+                       run_conj ? kLeanWaves * c.lean_wgs : 0,
+                       c.has_phrase ? kLeanWaves * c.lean_wgs_ph : 0,
+                       run_gen ? c.seg_grid : 0, fr, b->d_itemq, b->d_pub, b->d_desc, b->d_part, st));
     HIP_OK(hipEventRecord(b->ev[1], st));
     // general items on the second stream, lean items here; both drain their
     // own queue, then the streams join
@@ -1047,11 +834,11 @@ static int batch_run(wsr_handle* h, wsr_batch* b, const ShardEmit* se, const Own
     HIP_OK(hipStreamWaitEvent(b->st2, b->fork, 0));
     if (run_gen)
       HIP_OK(launch_segments(h->args, b->d_q(), b->d_plan, b->nq, b->d_ctr, b->d_events, b->d_evcnt,
-                             b->d_stats, b->seg_grid, fr, b->d_itemq, b->d_pub,
-                             b->gen_phrase ? b->d_ph : nullptr, b->st2));
-    uint32_t* lean_stats = b->d_stats + static_cast<size_t>(kStatStride) * b->seg_grid;
+                             b->d_stats, c.seg_grid, fr, b->d_itemq, b->d_pub,
+                             c.gen_phrase ? b->d_ph : nullptr, b->st2));
+    uint32_t* lean_stats = b->d_stats + static_cast<size_t>(kStatStride) * c.seg_grid;
     HIP_OK(hipEventRecord(b->join, b->st2));
-    if (b->has_phrase) {
+    if (c.has_phrase) {
       // The lean phrase queries' items run in the phrase instance (its
       // position check and registers) and the conjunctive lean items keep the
       // conjunctive instance's occupancy: the phrase launch on the batch
@@ -1062,7 +849,7 @@ static int batch_run(wsr_handle* h, wsr_batch* b, const ShardEmit* se, const Own
       HIP_OK(hipStreamWaitEvent(b->st_pad, b->fork, 0));
       if (run_conj)
         HIP_OK(launch_lean(h->args, b->d_q(), b->d_plan, b->nq, b->d_ctr, b->d_events, b->d_evcnt, lean_stats,
-                           b->lean_wgs, fr, b->d_itemq, b->d_pub, b->d_desc, false, b->two_conj, b->one_conj,
+                           c.lean_wgs, fr, b->d_itemq, b->d_pub, b->d_desc, false, c.two_conj, c.one_conj,
                            b->st_pad));
       if (pb) {   // the replay's end: behind the conjunctive launch that carried it
         HIP_OK(hipEventRecord(pb->xev[1], b->st_pad));
@@ -1072,11 +859,11 @@ static int batch_run(wsr_handle* h, wsr_batch* b, const ShardEmit* se, const Own
       FusedReplay frp = fr;
       frp.oj = OwnerJob{};
       HIP_OK(launch_lean(h->args, b->d_q(), b->d_plan, b->nq, b->d_ctr, b->d_events, b->d_evcnt,
-                         lean_stats + static_cast<size_t>(kStatStride) * kLeanWaves * b->lean_wgs,
-                         b->lean_wgs_ph, frp, b->d_itemq, b->d_pub, b->d_desc, true, b->two_ph, false, st));
+                         lean_stats + static_cast<size_t>(kStatStride) * kLeanWaves * c.lean_wgs,
+                         c.lean_wgs_ph, frp, b->d_itemq, b->d_pub, b->d_desc, true, c.two_ph, false, st));
     } else {
       HIP_OK(launch_lean(h->args, b->d_q(), b->d_plan, b->nq, b->d_ctr, b->d_events, b->d_evcnt, lean_stats,
-                         b->lean_wgs, fr, b->d_itemq, b->d_pub, b->d_desc, false, b->two_conj, b->one_conj, st));
+                         c.lean_wgs, fr, b->d_itemq, b->d_pub, b->d_desc, false, c.two_conj, c.one_conj, st));
     }
     HIP_OK(hipEventRecord(b->ev[4], st));
     if (pb && !pb_queued) {
@@ -1089,18 +876,18 @@ static int batch_run(wsr_handle* h, wsr_batch* b, const ShardEmit* se, const Own
       pb = nullptr;
     }
     HIP_OK(hipStreamWaitEvent(st, b->join, 0));
-    if (b->has_phrase) HIP_OK(hipStreamWaitEvent(st, b->join_ph, 0));
+    if (c.has_phrase) HIP_OK(hipStreamWaitEvent(st, b->join_ph, 0));
     HIP_OK(hipEventRecord(b->ev[2], st));
-    if (!se && b->has_wide)
+    if (!se && c.has_wide)
       HIP_OK(launch_wide_replay(b->d_q(), b->d_plan, b->nq, b->d_events, b->d_evcnt, b->d_hits, b->stride,
                                 b->d_nhits, st));
-    if (b->n_or) {
+    if (c.n_or) {
       // the disjunctive queries, after the plan's writes of their (empty) rows
       HIP_OK(hipMemsetAsync(b->d_orstat, 0, sizeof(unsigned long long) * kNumOrStats, st));
-      HIP_OK(launch_or_items(h->args, b->d_orq, b->d_oritem, b->or_items, b->or_nt_max, b->d_orev, b->d_orevcnt,
+      HIP_OK(launch_or_items(h->args, b->d_orq, b->d_oritem, c.or_items, c.or_nt_max, b->d_orev, b->d_orevcnt,
                              b->d_ctr, b->d_orstat, st));
-      HIP_OK(launch_or_replay(b->d_orq, static_cast<uint32_t>(b->n_or), b->d_oritem, b->d_orev, b->d_orevcnt,
-                              b->d_hits, b->stride, b->d_nhits, b->or_narrow, b->or_wide, st));
+      HIP_OK(launch_or_replay(b->d_orq, static_cast<uint32_t>(c.n_or), b->d_oritem, b->d_orev, b->d_orevcnt,
+                              b->d_hits, b->stride, b->d_nhits, c.or_narrow, c.or_wide, st));
     }
     HIP_OK(hipEventRecord(b->ev[3], st));
   } catch (const std::exception& e) {
@@ -1222,20 +1009,21 @@ int wsr_batch_stats_get(wsr_handle* h, wsr_batch* b, wsr_batch_stats* out) {
     if (x_join(b)) HIP_OK(hipEventSynchronize(b->xev[1]));   // a shard step's exchange + replay
     uint32_t ctr[kNumCounters];
     HIP_OK(hipMemcpy(ctr, b->d_ctr, sizeof ctr, hipMemcpyDeviceToHost));
-    const int rows = b->seg_grid + kLeanWaves * (b->lean_wgs + (b->has_phrase ? b->lean_wgs_ph : 0));
+    const int rows = b->cls.seg_grid + kLeanWaves * (b->cls.lean_wgs + (b->cls.has_phrase ? b->cls.lean_wgs_ph : 0));
     std::vector<uint32_t> ws(static_cast<size_t>(kStatStride) * rows);
     HIP_OK(hipMemcpy(ws.data(), b->d_stats, ws.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     uint64_t sv = 0, db = 0, ob = 0;
     for (int i = 0; i < rows; ++i) {
       // (rows of a kernel the last run did not launch hold an earlier run's values)
-      if (i < b->seg_grid ? !b->ran_gen : (i < b->seg_grid + kLeanWaves * b->lean_wgs && !b->ran_conj)) continue;
+      const bool conj_row = i >= b->cls.seg_grid && i < b->cls.seg_grid + kLeanWaves * b->cls.lean_wgs;
+      if (i < b->cls.seg_grid ? !b->launched.gen : (conj_row && !b->launched.conj)) continue;
       sv += ws[kStatStride * i]; db += ws[kStatStride * i + 1]; ob += ws[kStatStride * i + 2];
     }
     out->work_items = ctr[kCtrItems];
     out->survivors = sv;
     out->driver_blocks = db;
     out->other_blocks = ob;
-    out->algo_bytes = b->algo_static + sv;
+    out->algo_bytes = b->cls.algo_static + sv;
     {
       const uint32_t items = ctr[kCtrItems];
       std::vector<uint32_t> ec(items);
@@ -1266,7 +1054,7 @@ int wsr_batch_stats_get(wsr_handle* h, wsr_batch* b, wsr_batch_stats* out) {
 int wsr_batch_or_stats_get(wsr_handle* h, wsr_batch* b, wsr_or_stats* out) {
   if (!h || !b || !out || !b->ran) return fail(WSR_E_INVALID, "batch has not been run");
   *out = wsr_or_stats{};
-  if (!b->n_or) return WSR_OK;
+  if (!b->cls.n_or) return WSR_OK;
   std::lock_guard<std::mutex> g(h->mu);
   try {
     HIP_OK(hipSetDevice(h->device));
@@ -1787,7 +1575,7 @@ static int owner_replay_meta_on(wsr_handle* h, wsr_batch* b, int32_t q0, int32_t
     HIP_OK(hipSetDevice(h->device));
     HIP_OK(launch_owner_replay_meta(b->d_q(), q0, nq_owned, n_shards, d_rmeta, meta_stride, stride,
                                     static_cast<const Event*>(d_recv), b->d_hits, b->stride, b->d_nhits,
-                                    b->d_ctr, b->has_wide, st));
+                                    b->d_ctr, b->cls.has_wide, st));
   } catch (const std::exception& e) {
     return fail(WSR_E_HIP, e.what());
   }
@@ -1814,7 +1602,7 @@ static uint64_t region_events_of(int32_t q_per_owner, int64_t slot) {
 static int check_step(wsr_handle* h, wsr_batch* b, int W, int32_t q_per_owner, int64_t slot) {
   if (!h || !b || W < 1 || q_per_owner <= 0 || slot <= 0 || static_cast<int64_t>(q_per_owner) * W != b->nq)
     return fail(WSR_E_INVALID, "bad shard_step arguments (the batch must hold world * q_per_owner queries)");
-  if (b->has_or) return fail(WSR_E_INVALID, "a doc-range shard step cannot run a disjunctive query");
+  if (b->cls.has_or) return fail(WSR_E_INVALID, "a doc-range shard step cannot run a disjunctive query");
   if (W > kMaxOwners) return fail(WSR_E_LIMIT, "more than kMaxOwners ranks");
   if (static_cast<uint64_t>(slot) > 0xFFFFFFFFull) return fail(WSR_E_LIMIT, "slot over 2^32 events");
   return WSR_OK;
@@ -2037,7 +1825,7 @@ int wsr_shard_steps(wsr_handle* h, wsr_batch* const* bs, int32_t n, wsr_comm* c,
       for (size_t i = 0; i < P->bs.size() && i < static_cast<size_t>(n); ++i) {
         const wsr_batch* pb = P->bs[i];
         if (P->queued[i]) continue;
-        if (pb->has_wide) continue;   // (the LDS heap: on the communicator's stream)
+        if (pb->cls.has_wide) continue;   // (the LDS heap: on the communicator's stream)
         const Event* recv = SP.recv + rP * i;
         oj[i] = OwnerJob{pb->d_q(), reinterpret_cast<const int32_t*>(recv), recv + meta_events, pb->d_hits,
                          pb->d_nhits, pb->d_ctr, runP * (sizeof(Event) / sizeof(int32_t)), runP,
@@ -2158,7 +1946,7 @@ int wsr_shard_step_replay(wsr_handle* h, wsr_batch* b, int32_t rank, int32_t wor
       !b->x_fused || b->x_world != world || b->x_qpr != q_per_owner || b->x_slot != slot ||
       static_cast<int64_t>(q_per_owner) * world != b->nq)
     return fail(WSR_E_INVALID, "call wsr_shard_step_emit with the same world, q_per_owner and slot first");
-  if (b->has_or) return fail(WSR_E_INVALID, "a doc-range shard step cannot run a disjunctive query");
+  if (b->cls.has_or) return fail(WSR_E_INVALID, "a doc-range shard step cannot run a disjunctive query");
   try {
     HIP_OK(hipSetDevice(h->device));
     HIP_OK(hipMemcpyAsync(b->d_xrecv, host_recv, sizeof(Event) * region_events_of(q_per_owner, slot) * world,
@@ -2179,8 +1967,8 @@ int wsr_shard_step_replay_deferred(wsr_handle* h, wsr_batch* b, int32_t rank, in
       !b->x_fused || b->x_world != world || b->x_qpr != q_per_owner || b->x_slot != slot ||
       static_cast<int64_t>(q_per_owner) * world != b->nq)
     return fail(WSR_E_INVALID, "call wsr_shard_step_emit with the same world, q_per_owner and slot first");
-  if (b->has_or) return fail(WSR_E_INVALID, "a doc-range shard step cannot run a disjunctive query");
-  if (b->has_wide)   // (the LDS heap: the replay launch of its own)
+  if (b->cls.has_or) return fail(WSR_E_INVALID, "a doc-range shard step cannot run a disjunctive query");
+  if (b->cls.has_wide)   // (the LDS heap: the replay launch of its own)
     return wsr_shard_step_replay(h, b, rank, world, q_per_owner, slot, host_recv);
   try {
     HIP_OK(hipSetDevice(h->device));
@@ -2303,8 +2091,8 @@ int wsr_debug_wg_stats(wsr_handle* h, wsr_batch* b, uint32_t* out, int32_t max_w
   if (!h || !b) return fail(WSR_E_INVALID, "null argument");
   std::lock_guard<std::mutex> g(h->mu);
   // general workgroups, then lean waves (the conjunctive instance's, then the phrase instance's);
-  // the rows of a kernel the last run did not launch (b->ran_conj / ran_gen) are stale
-  const int rows = b->seg_grid + kLeanWaves * (b->lean_wgs + (b->has_phrase ? b->lean_wgs_ph : 0));
+  // the rows of a kernel the last run did not launch (b->launched) are stale
+  const int rows = b->cls.seg_grid + kLeanWaves * (b->cls.lean_wgs + (b->cls.has_phrase ? b->cls.lean_wgs_ph : 0));
   if (n_wg) *n_wg = rows;
   if (stride) *stride = kStatStride;
   if (!out) return WSR_OK;
@@ -2322,12 +2110,13 @@ int wsr_debug_wg_stats(wsr_handle* h, wsr_batch* b, uint32_t* out, int32_t max_w
 
 int wsr_debug_batch_class(wsr_handle* h, wsr_batch* b, uint32_t* flags) {
   if (!h || !b || !flags) return fail(WSR_E_INVALID, "null argument");
-  *flags = (b->two_conj ? WSR_CLASS_TWO_CONJ : 0u) | (b->one_conj ? WSR_CLASS_ONE_CONJ : 0u) |
-           (b->has_phrase ? WSR_CLASS_HAS_PHRASE : 0u) | (b->two_ph ? WSR_CLASS_TWO_PH : 0u) |
-           (b->has_wide ? WSR_CLASS_HAS_WIDE : 0u) | (b->gen_phrase ? WSR_CLASS_GEN_PHRASE : 0u) |
-           (b->has_conj_lean ? WSR_CLASS_HAS_CONJ_LEAN : 0u) | (b->has_gen ? WSR_CLASS_HAS_GEN : 0u) |
-           (b->has_or ? WSR_CLASS_HAS_OR : 0u) | (b->ran_conj ? WSR_CLASS_RAN_CONJ : 0u) |
-           (b->ran_gen ? WSR_CLASS_RAN_GEN : 0u);
+  const BatchClass& c = b->cls;
+  *flags = (c.two_conj ? WSR_CLASS_TWO_CONJ : 0u) | (c.one_conj ? WSR_CLASS_ONE_CONJ : 0u) |
+           (c.has_phrase ? WSR_CLASS_HAS_PHRASE : 0u) | (c.two_ph ? WSR_CLASS_TWO_PH : 0u) |
+           (c.has_wide ? WSR_CLASS_HAS_WIDE : 0u) | (c.gen_phrase ? WSR_CLASS_GEN_PHRASE : 0u) |
+           (c.has_conj_lean ? WSR_CLASS_HAS_CONJ_LEAN : 0u) | (c.has_gen ? WSR_CLASS_HAS_GEN : 0u) |
+           (c.has_or ? WSR_CLASS_HAS_OR : 0u) | (b->launched.conj ? WSR_CLASS_RAN_CONJ : 0u) |
+           (b->launched.gen ? WSR_CLASS_RAN_GEN : 0u);
   return WSR_OK;
 }
 

@@ -151,6 +151,43 @@ struct QueryIn {
 static_assert(sizeof(QueryIn) == 80, "QueryIn layout");
 constexpr int32_t kQueryPhrase = 1;
 
+// Planning constants of the device plan (plan_query_kernel) that the host's
+// upload plan (batch_plan.cc) sizes the grids and workspaces by.
+constexpr int kLeanWaves = 4;   // independent waves per lean_kernel workgroup
+// Target block decodes per work item, for every class (lean, general,
+// phrase); bounds seg_blocks (< 64).  Phrase items have been this long since
+// round 3 (5 blocks before, while every conjunctive survivor ran the position
+// check; now only the running top-k's candidates do, and longer items prune
+// more: C5 leg 3.50 -> 4.95 M q/s at 63 blocks, 16: 4.27, 32: 4.56 M,
+// profiles/r03_phrase_item_ab.txt).
+constexpr int kSegCost = 63;
+static_assert(kSegCost < 64, "a segment's driver directory is one entry per lane");
+// A single-term item spans up to this many items' worth of blocks, which
+// single_segment runs window by window: most of its blocks are skipped by
+// their block bounds, so a short item would be mostly fixed cost.
+constexpr int kSingleWindows = 8;
+
+// The class rule, stated once for the device plan and the kernels
+// (kernels.hip) and for the host's upload plan (batch_plan.cc); constexpr, so
+// callable from device code.  A query's driver is its list of the fewest
+// blocks here (the first of equals).
+// Other list B is probed through its bitmap or buckets when it has them and is
+// at least dense_ratio times as long as the driver (then a block decode per
+// probe would mostly decode postings nobody asks for).  Image: what holds the
+// engine's dense_ratio (the kernels' IndexArgs, the host plan's ImageView).
+template <class Image>
+constexpr bool probe_by_bitmap(const Image& ix, bool has_bm, uint32_t nblk_b, uint32_t nblk_driver) {
+  return has_bm && static_cast<float>(nblk_b) >= ix.dense_ratio * static_cast<float>(nblk_driver);
+}
+// A one-term "phrase" is a plain term.
+constexpr bool is_phrase_query(int32_t n_terms, int32_t flags) { return n_terms > 1 && (flags & kQueryPhrase); }
+// Lean (lean_kernel; the rest: segment_kernel): every other list probed by
+// bitmap, and not a phrase of more than two terms (the lean kernel checks
+// positions of two-term phrases only, in registers).
+constexpr bool is_lean_query(bool others_by_bitmap, int32_t n_terms, int32_t flags) {
+  return others_by_bitmap && !(n_terms > 2 && (flags & kQueryPhrase));
+}
+
 // Positions of one posting list in the image (phrase queries).  The list's
 // position cozy box (flash_engine_dumper.h:78-104: full packs of 128 entries,
 // then one VInts blob) is copied byte-identical to pos_blob at `base`; pack i

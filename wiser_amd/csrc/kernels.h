@@ -72,25 +72,13 @@ constexpr int kPlanBucketShift = 12;
 constexpr uint32_t kPlanLean = 1u << 16;
 constexpr uint32_t kPlanPhrase = 1u << 17;
 static_assert(kMaxQueryTerms <= static_cast<int>(kPlanSlotMask) + 1, "driver slot field");
-constexpr int kLeanWaves = 4;   // independent waves per lean_kernel workgroup
 // per-workgroup statistics written by the segment kernels (no atomics):
 // stats[wg * kStatStride + {0 survivors, 1 driver blocks, 2 other blocks}]
 constexpr int kStatStride = 4;
 enum { kErrLimit = 1, kErrCapacity = 2, kErrExchange = 4, kErrClass = 8 };
 constexpr int kMaxOwners = 1024;   // doc-range shards (ranks) of one exchange
 
-// Target block decodes per work item, for every class (lean, general,
-// phrase); bounds seg_blocks (< 64).  Phrase items have been this long since
-// round 3 (5 blocks before, while every conjunctive survivor ran the position
-// check; now only the running top-k's candidates do, and longer items prune
-// more: C5 leg 3.50 -> 4.95 M q/s at 63 blocks, 16: 4.27, 32: 4.56 M,
-// profiles/r03_phrase_item_ab.txt).
-constexpr int kSegCost = 63;
-static_assert(kSegCost < 64, "a segment's driver directory is one entry per lane");
-// A single-term item spans up to this many items' worth of blocks, which
-// single_segment runs window by window: most of its blocks are skipped by
-// their block bounds, so a short item would be mostly fixed cost.
-constexpr int kSingleWindows = 8;
+// (kLeanWaves, kSegCost and kSingleWindows: engine_types.h, with the class rule)
 // Driver blocks per item of a phrase query at most: a batch's phrase items
 // are its tail when they are few (the realistic mix in log order: 15.4 -> 16.5
 // M q/s at 32 against 63, C5 unchanged; 16: 16.0 / 8.5 M, round 5).  Since the

@@ -275,16 +275,15 @@ __device__ __forceinline__ uint32_t find_block(const uint32_t* last, uint32_t cu
 }
 
 // ---------------------------------------------------------- dense lists --
-// Other list B is probed through its rank bitmap when it has one and is at
-// least dense_ratio times as long as the driver (then a block decode per
-// probe would mostly decode postings nobody asks for).  A bitmap probe round
+// Other list B is probed through its rank bitmap by the shared rule
+// (probe_by_bitmap, engine_types.h).  A bitmap probe round
 // adds nothing to an item's plan cost: a lean item is kSegCost driver blocks
 // (with the pre-probe bound and the floor refresh, longer items prune more and
 // carry less fixed work per block: main leg 26.6 -> 28.0 M q/s against
 // 42-block items, profiles/r02_sy_item_size_ab.txt).
 __device__ __forceinline__ bool use_dense(const IndexArgs& ix, bool has_bm, uint32_t nblk_b,
                                           uint32_t nblk_driver) {
-  return has_bm && static_cast<float>(nblk_b) >= ix.dense_ratio * static_cast<float>(nblk_driver);
+  return probe_by_bitmap(ix, has_bm, nblk_b, nblk_driver);
 }
 
 // A bitmap entry as loaded for a probe: x = rank, y = mask word (two
@@ -599,14 +598,13 @@ __global__ __launch_bounds__(kPlanThreads) void plan_query_kernel(IndexArgs ix, 
         if (L.nblk < o_nb) { o1 = s; o_nb = L.nblk; }
       }
     }
-    // a phrase query of more than two terms runs in the general class (the
-    // lean kernel checks positions of two-term phrases only, in registers)
-    if (nt > 2 && (q.flags & kQueryPhrase)) lean = false;
+    // (so far: every other list probed by bitmap)
+    lean = is_lean_query(lean, nt, q.flags);
     if (ok) {
       uint32_t seg = static_cast<uint32_t>(kSegCost / cost);
       seg = seg > ix.seg_cap ? ix.seg_cap : seg;
       if (nt == 1) seg *= kSingleWindows;   // (single_segment: windows of 64 blocks)
-      if (nt > 1 && (q.flags & kQueryPhrase)) seg = seg > kPhraseSegCap ? kPhraseSegCap : seg;
+      if (is_phrase_query(nt, q.flags)) seg = seg > kPhraseSegCap ? kPhraseSegCap : seg;
       seg = seg < 1 ? 1 : (seg > nd ? nd : seg);
       // cost class of one item (log2 of its block decodes, plus a fixed part
       // for the per-item setup): the queue hands out heavy items first
@@ -617,7 +615,7 @@ __global__ __launch_bounds__(kPlanThreads) void plan_query_kernel(IndexArgs ix, 
       const uint32_t bucket = n_items >= kHeavyQueryItems ? static_cast<uint32_t>(kCostBuckets - 1)
                                                           : min(lg - 2u, static_cast<uint32_t>(kCostBuckets - 2));
       // (a lean phrase query has two terms: the one-term "phrase" is a plain term)
-      const bool lean_ph = lean && nt > 1 && (q.flags & kQueryPhrase);
+      const bool lean_ph = lean && is_phrase_query(nt, q.flags);
       p.driver = d | (bucket << kPlanBucketShift) | (lean ? kPlanLean : 0u) | (lean_ph ? kPlanPhrase : 0u);
       p.seg_blocks = seg;
       p.n_items = n_items;
@@ -2784,7 +2782,7 @@ __global__ __launch_bounds__(64, kSegWaves) void segment_kernel(IndexArgs ix, co
     // workgroup's slice of ph_all, then the positions are checked
     const bool phrase = kPhrase && nt > 1 && (uni(static_cast<uint32_t>(qs[qi].flags)) & kQueryPhrase);
     // (the conjunctive instance runs a batch whose phrase queries are all lean,
-    // by the host's restatement of the class rule: a general phrase item here
+    // by the host's evaluation of the class rule: a general phrase item here
     // would lose its position check, so it fails the batch loudly instead)
     if (!kPhrase && nt > 1 && (uni(static_cast<uint32_t>(qs[qi].flags)) & kQueryPhrase)) {
       if (l == 0) atomicOr(&counters[kCtrError], static_cast<uint32_t>(kErrClass));
