@@ -8,6 +8,7 @@ equal the oracle bit for bit."""
 import ctypes as C
 import os
 import random
+from collections import namedtuple
 
 import pytest
 
@@ -16,15 +17,18 @@ from conftest import DATA
 pytestmark = pytest.mark.gpu
 
 
-def open_shards(index_dir, world, positions=False):
-    """The W shard engines of a doc-range split of index_dir."""
+def open_shards(index_dir, world, positions=False, ranges=None):
+    """The W shard engines of a doc-range split of index_dir (ranges: a
+    hand-made tiling of [0, n_docs) instead of the even split)."""
     import wiser_amd as w
     from wiser_amd.shard import index_doc_count, shard_range
     n = index_doc_count(index_dir)
+    if ranges is None:
+        ranges = [shard_range(n, r, world) for r in range(world)]
     engs = []
     try:
-        for r in range(world):
-            e = w.VacuumEngine(index_dir, doc_range=shard_range(n, r, world), positions=positions)
+        for rg in ranges:
+            e = w.VacuumEngine(index_dir, doc_range=tuple(rg), positions=positions)
             e.Load()
             engs.append(e)
     except Exception:
@@ -34,6 +38,59 @@ def open_shards(index_dir, world, positions=False):
     return engs
 
 
+# ---- the region moves of a step, shared by the helpers below ---------------
+def emit_regions(engs, batches, qpr, slot):
+    """Every shard's wsr_shard_step_emit -> per shard its send regions, an
+    int64 array [world, words of a region] (region o: for owner o)."""
+    import numpy as np
+    from wiser_amd._capi import check, lib
+    world = len(engs)
+    rb = C.c_uint64()
+    check(lib.wsr_shard_step_regions(qpr, slot, C.byref(rb)))
+    words = rb.value // 8
+    sends = []
+    for e, b in zip(engs, batches):
+        send = np.full(world * words, -7, dtype=np.int64)
+        check(lib.wsr_shard_step_emit(e._h, b._b, world, qpr, slot, C.c_void_p(send.ctypes.data)))
+        sends.append(send.reshape(world, words))
+    return sends
+
+
+def slot_from_first_emission(engs, batches, qpr):
+    """The slot sized from a first emission's fill (wsr_shard_fill), as
+    bench.py does."""
+    from wiser_amd._capi import check, lib
+    from wiser_amd.shard import slot_for_fill
+    world = len(engs)
+    emit_regions(engs, batches, qpr, 64 * qpr)
+    fill = 0
+    for e, b in zip(engs, batches):
+        tot = (C.c_int64 * world)()
+        check(lib.wsr_shard_fill(e._h, b._b, world, tot))
+        fill = max(fill, max(tot))
+    return slot_for_fill(fill, qpr)
+
+
+def replay_owner(engs, batches, sends, o, qpr, slot, stride):
+    """The all-to-all's move for owner o (region o of rank g -> region g of
+    rank o), its wsr_shard_step_replay and the fetch of its range -> (the
+    fetch's return code, [[(doc, score)]] of the owner's qpr queries)."""
+    import numpy as np
+    from wiser_amd import _capi
+    from wiser_amd._capi import check, lib
+    world = len(engs)
+    recv = np.ascontiguousarray(np.stack([sends[g][o] for g in range(world)]))
+    e, b = engs[o], batches[o]
+    check(lib.wsr_shard_step_replay(e._h, b._b, o, world, qpr, slot, C.c_void_p(recv.ctypes.data)))
+    hits = (_capi.Hit * (qpr * stride))()
+    nh = (C.c_int32 * qpr)()
+    rc = lib.wsr_batch_fetch_range(e._h, b._b, o * qpr, qpr, hits, nh)
+    if rc:
+        return rc, []
+    return 0, [[(hits[i * stride + j].doc_id, hits[i * stride + j].score) for j in range(nh[i])]
+               for i in range(qpr)]
+
+
 def _run_step_regions(index_dir, queries, k, world, slot, phrase=False, engines=None):
     """wsr_shard_step's own buffers at W > 1: every shard runs
     wsr_shard_step_emit (fused emission into the engine's region buffer, owner
@@ -41,11 +98,9 @@ def _run_step_regions(index_dir, queries, k, world, slot, phrase=False, engines=
     regions are moved exactly as ncclAllToAll moves them (region o of rank g ->
     region g of rank o), and wsr_shard_step_replay replays each owner.  slot
     None: sized from a first emission's fill (wsr_shard_fill), as bench.py does."""
-    import numpy as np
     import wiser_amd as w
     from wiser_amd import _capi
-    from wiser_amd._capi import check, lib
-    from wiser_amd.shard import slot_for_fill
+    from wiser_amd._capi import lib
     qpr = len(queries) // world
     queries = queries[:qpr * world]
     engs = engines or open_shards(index_dir, world, positions=phrase)
@@ -58,38 +113,15 @@ def _run_step_regions(index_dir, queries, k, world, slot, phrase=False, engines=
             b = w.ResidentBatch(e, len(queries), k)
             batches.append(b)
             b.upload(arr)
-
-        def emit(slot):
-            rb = C.c_uint64()
-            check(lib.wsr_shard_step_regions(qpr, slot, C.byref(rb)))
-            words = rb.value // 8
-            sends = []
-            for e, b in zip(engs, batches):
-                send = np.full(world * words, -7, dtype=np.int64)
-                check(lib.wsr_shard_step_emit(e._h, b._b, world, qpr, slot, C.c_void_p(send.ctypes.data)))
-                sends.append(send.reshape(world, words))
-            return sends
         if slot is None:
-            sends = emit(64 * qpr)
-            fill = 0
-            for e, b in zip(engs, batches):
-                tot = (C.c_int64 * world)()
-                check(lib.wsr_shard_fill(e._h, b._b, world, tot))
-                fill = max(fill, max(tot))
-            slot = slot_for_fill(fill, qpr)
-        sends = emit(slot)
+            slot = slot_from_first_emission(engs, batches, qpr)
+        sends = emit_regions(engs, batches, qpr, slot)
         out = []
         for o in range(world):
-            recv = np.ascontiguousarray(np.stack([sends[g][o] for g in range(world)]))
-            e, b = engs[o], batches[o]
-            check(lib.wsr_shard_step_replay(e._h, b._b, o, world, qpr, slot, C.c_void_p(recv.ctypes.data)))
-            hits = (_capi.Hit * (qpr * k))()
-            nh = (C.c_int32 * qpr)()
-            rc = lib.wsr_batch_fetch_range(e._h, b._b, o * qpr, qpr, hits, nh)
+            rc, got = replay_owner(engs, batches, sends, o, qpr, slot, k)
             if rc:
                 raise _capi.WiserError(rc, lib.wsr_last_error().decode())
-            for i in range(qpr):
-                out.append([(hits[i * k + j].doc_id, hits[i * k + j].score) for j in range(nh[i])])
+            out += got
         return queries, out
     finally:
         for b in batches:
@@ -97,6 +129,55 @@ def _run_step_regions(index_dir, queries, k, world, slot, phrase=False, engines=
         if engines is None:
             for e in engs:
                 e.close()
+
+
+ShardRun = namedtuple("ShardRun", "cls stats")   # of one shard: launch_class() after the upload, stats() of the step
+
+
+def run_step_items(engs, items, item_blocks, neutral):
+    """One shard step of a class-pure batch of test_gpu_instances.Item (per-item
+    k, phrase flag, raw (n_terms, k) overrides) over the shard engines engs,
+    whose ranges tile [0, n_docs): the batch is padded to a multiple of the
+    world with the neutral queries `neutral` (no query is dropped); every shard
+    gets a ResidentBatch of hit stride = the largest k, set_item_blocks, the
+    upload, and emits (slot from a first emission's fill); the regions move as
+    in _run_step_regions; every owner replays and fetches its range.
+    -> ([[(doc, score)]] per item, the padding left out; [ShardRun] per shard;
+    [return code of every owner's fetch])"""
+    import wiser_amd as w
+    from wiser_amd import _capi
+    from wiser_amd.shard import index_doc_count
+    from test_gpu_instances import _raw_query
+    world = len(engs)
+    ranges = [tuple(e.doc_range) for e in engs]
+    n_docs = index_doc_count(engs[0].engine_dir_path)
+    assert ranges[0][0] == 0 and ranges[-1][1] == n_docs, ranges
+    assert all(a[1] == b[0] for a, b in zip(ranges, ranges[1:])) and all(lo < hi for lo, hi in ranges), ranges
+    padded = list(items)
+    while len(padded) % world:
+        padded.append(neutral[(len(padded) - len(items)) % len(neutral)])
+    qpr = len(padded) // world
+    stride = max(1, max(it.k for it in padded))
+    batches, runs = [], []
+    try:
+        for e in engs:
+            b = w.ResidentBatch(e, len(padded), stride)
+            batches.append(b)
+            b.set_item_blocks(item_blocks)
+            b.upload((_capi.Query * len(padded))(*[_raw_query(e, it) for it in padded]))
+            runs.append(b.launch_class())
+        slot = slot_from_first_emission(engs, batches, qpr)
+        sends = emit_regions(engs, batches, qpr, slot)
+        out, rcs = [], []
+        for o in range(world):
+            rc, got = replay_owner(engs, batches, sends, o, qpr, slot, stride)
+            rcs.append(rc)
+            out += got if not rc else [None] * qpr
+        runs = [ShardRun(cls, b.stats()) for cls, b in zip(runs, batches)]
+        return out[:len(items)], runs, rcs
+    finally:
+        for b in batches:
+            b.close()
 
 
 @pytest.mark.parametrize("world", [1, 2, 3, 4])
