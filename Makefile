@@ -7,7 +7,8 @@ JOBS    ?= 8
 LIB     := wiser_amd/_lib/libwiser_hip.so
 ORACLE  := oracle/_build/liboracle.so
 SRCS    := wiser_amd/csrc/writer.cc wiser_amd/csrc/index.cc wiser_amd/csrc/engine.cc \
-           wiser_amd/csrc/batch_plan.cc wiser_amd/csrc/server.cc wiser_amd/csrc/docstore.cc \
+           wiser_amd/csrc/shard_exchange.cc wiser_amd/csrc/batch_plan.cc wiser_amd/csrc/server.cc \
+           wiser_amd/csrc/docstore.cc \
            wiser_amd/csrc/snippet.cc wiser_amd/csrc/kernels.hip
 HDRS    := $(wildcard wiser_amd/csrc/*.h) include/wiser_hip.h
 OBJDIR  := wiser_amd/_lib/obj
@@ -23,11 +24,13 @@ CALIB   := wiser_amd/_lib/calib_ea
 DICT    := wiser_amd/_lib/dict_check
 DEVMEM  := wiser_amd/_lib/dev_mem_check
 BPLAN   := wiser_amd/_lib/batch_plan_check
+SLAYOUT := wiser_amd/_lib/shard_layout_check
 
-# (the buffer owner's and the upload plan's checks are tests of those files alone:
-# a tree whose tests/ does not hold their sources still builds everything else)
+# (the buffer owner's, the upload plan's and the shard layout's checks are tests of those files
+# alone: a tree whose tests/ does not hold their sources still builds everything else)
 all: $(LIB) $(ORACLE) $(CLI) $(CALIB) $(DICT) $(if $(wildcard tests/cpp/dev_mem_check.cc),$(DEVMEM)) \
-     $(if $(wildcard tests/cpp/batch_plan_check.cc),$(BPLAN))
+     $(if $(wildcard tests/cpp/batch_plan_check.cc),$(BPLAN)) \
+     $(if $(wildcard tests/cpp/shard_layout_check.cc),$(SLAYOUT))
 
 # CPU check of the term dictionary (tests/test_dictionary.py)
 $(DICT): tests/cpp/dict_check.cc wiser_amd/csrc/index.h $(LIB)
@@ -43,6 +46,12 @@ $(BPLAN): tests/cpp/batch_plan_check.cc wiser_amd/csrc/batch_plan.cc wiser_amd/c
           wiser_amd/csrc/engine_types.h include/wiser_hip.h
 	@mkdir -p wiser_amd/_lib
 	$(CXX) -O2 -std=c++17 -Wall -o $@ tests/cpp/batch_plan_check.cc wiser_amd/csrc/batch_plan.cc
+
+# CPU check of the shard exchange's region layout and its two device views (tests/test_shard_layout.py):
+# no HIP, no engine
+$(SLAYOUT): tests/cpp/shard_layout_check.cc wiser_amd/csrc/shard_layout.h wiser_amd/csrc/engine_types.h
+	@mkdir -p wiser_amd/_lib
+	$(CXX) -O2 -std=c++17 -Wall -o $@ tests/cpp/shard_layout_check.cc
 
 # counter calibration (profiles only): known-byte reads for rocprofv3 --pmc
 $(CALIB): scripts/calib_ea.hip

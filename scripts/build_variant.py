@@ -16,7 +16,8 @@ import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRCS = ["writer.cc", "index.cc", "engine.cc", "batch_plan.cc", "server.cc", "docstore.cc", "snippet.cc", "kernels.hip"]
+SRCS = ["writer.cc", "index.cc", "engine.cc", "shard_exchange.cc", "batch_plan.cc", "server.cc", "docstore.cc",
+        "snippet.cc", "kernels.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall",
          "-Wno-unused-function"]
 

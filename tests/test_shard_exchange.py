@@ -75,7 +75,7 @@ def _worker(rank, world, port, index_dir, queries, k, result_q):
     # the product's regions: owner o's queries o*qpr .. o*qpr+qpr-1
     slot = max(1, max(sum(counts[o_ * qpr:(o_ + 1) * qpr]) for o_ in range(world)) + 3)
     rw = 2 * region_events(qpr, slot)            # int64 words per region
-    meta_words = 2 * ((qpr + 1) // 2)
+    meta_words = 2 * region_events(qpr, 0)       # ... of its meta block (a region without a slot)
     send = torch.full((world * rw,), -7, dtype=torch.int64)
     ev = 0
     for o_ in range(world):

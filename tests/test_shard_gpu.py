@@ -354,7 +354,7 @@ def test_native_rccl_failed_group_flushes_predecessor(synth_small, monkeypatch):
     """a step group whose emission fails after it has taken the
     deferred replays of an earlier group must still enqueue them: the earlier
     group's batches are then fetched (bit-exact) and destroyed without waiting
-    forever in x_join.  The failure is injected (wsr_debug_fail_runs)."""
+    forever in their join (ShardExchange::join).  The failure is injected (wsr_debug_fail_runs)."""
     import wiser_amd as w
     from wiser_amd import _capi
     from wiser_amd._capi import lib

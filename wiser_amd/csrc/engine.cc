@@ -1,5 +1,6 @@
 // C ABI (include/wiser_hip.h) over the HIP engine: index load + HBM upload,
-// resident query batches, kernel launches, result download.
+// resident query batches, kernel launches, result download.  (Doc-range shard
+// steps and their communicators: shard_exchange.cc.)
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 #include <dlfcn.h>
@@ -8,42 +9,24 @@
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
-#include <condition_variable>
 #include <cmath>
 #include <cstring>
 #include <memory>
 #include <cstdlib>
-#include <deque>
-#include <map>
 #include <mutex>
 #include <stdexcept>
 #include <string>
 #include <thread>
 #include <vector>
 
-#include "../../include/wiser_hip.h"
-#include "batch_plan.h"
-#include "dev_mem.h"
-#include "engine_types.h"
+#include "engine_impl.h"
 #include "format.h"
-#include "index.h"
-#include "kernels.h"
-#include "snippet.h"
 #include "writer.h"
 
 using namespace wiser;
 
-namespace {
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
-}  // namespace
-
 namespace wiser {
+thread_local std::string g_err;
 // (server.cc: a request failed on the dispatcher thread; its caller's thread
 // gets the message)
 void set_last_error(const std::string& msg) { g_err = msg; }
@@ -59,165 +42,7 @@ uint64_t dev_upload(gpu::DevBuf<T>& dst, const std::vector<T, A>& src) {
   return dst.bytes();
 }
 
-// tuning knobs read once per wsr_open (unset or unparsable: the default)
-double env_number(const char* name, double dflt) {
-  const char* v = std::getenv(name);
-  if (!v || !*v) return dflt;
-  char* end = nullptr;
-  const double x = std::strtod(v, &end);
-  return (end && *end == 0 && x >= 0) ? x : dflt;
-}
-
 }  // namespace
-
-struct wsr_handle {
-  std::mutex mu;
-  int device = 0;
-  gpu::Stream stream;
-  VacuumIndex idx;
-  DocStore docs;                    // my.fdx / my.fdt when the index has them (snippets)
-  std::unique_ptr<SkipRowCache> rows;   // decoded skip rows for the snippet stage
-  std::mutex pool_mu;                   // wsr_search_batch's reusable batches
-  std::vector<wsr_batch*> pool;
-  IndexArgs args{};
-  gpu::DevBuf<uint8_t> d_blob;
-  gpu::DevBuf<ListDev> d_lists;
-  gpu::DevBuf<BlockDev> d_blocks;
-  gpu::DevBuf<uint32_t> d_last, d_meta;
-  gpu::DevBuf<uint8_t> d_c4;
-  gpu::DevBuf<double> d_cache;
-  gpu::DevBuf<DenseEnt> d_dense;
-  gpu::DevBuf<uint32_t> d_dense_rk;   // the bitmap entries' rank records
-  gpu::DevBuf<uint32_t> d_bkt;        // offset buckets (entries and offset bytes)
-  gpu::DevBuf<uint8_t> d_tf8, d_plen, d_impact;
-  gpu::DevBuf<float> d_bmax;
-  gpu::DevBuf<uint32_t> d_tails;
-  gpu::DevBuf<uint8_t> d_pos_blob;    // positions (opened with wsr_open_opts::positions)
-  gpu::DevBuf<PosDev> d_pos_lists;
-  gpu::DevBuf<uint32_t> d_pos_pk, d_pos_tail, d_pos_start;
-  gpu::DevBuf<uint8_t> d_blm;
-  gpu::DevBuf<uint32_t> d_blm_hash;
-  bool positions = false;
-  uint32_t dense_lists = 0;
-  wsr_image_info info{};            // HBM bytes of the image's buffers
-  std::vector<ListDev> lists;       // host copy of the directory heads
-  std::vector<uint64_t> list_bytes; // docid+tf span bytes per list in this image
-  std::vector<uint64_t> pos_bytes;  // position box bytes per list (positions on)
-  std::vector<BlockDev> blocks;     // host copy (debug decode)
-  std::vector<uint32_t> meta;
-  // host-exchange owner replays deferred into a later batch run's lean kernel
-  // (wsr_shard_step_replay_deferred), oldest first
-  std::mutex hdef_mu;
-  std::deque<wsr_batch*> hdef_q;
-  int grid = 0;        // general segment kernel: workgroups (one wave each)
-  int lean_wgs = 0;    // lean kernel: workgroups of kLeanWaves waves
-  int lean_wgs_ph = 0; // ... its phrase instance's
-  int lean_wgs_two = 0; // ... its two-term instance's (one workgroup per CU past residency)
-  int gen_cap = 0;     // general workgroups launched at most
-  // what the upload plan (batch_plan.h) reads of the handle
-  ImageView view() const {
-    ImageView v;
-    v.lists = lists.data();
-    v.n_lists = lists.size();
-    v.blocks = blocks.data();
-    v.n_blocks = blocks.size();
-    v.list_bytes = list_bytes.data();
-    v.pos_bytes = pos_bytes.empty() ? nullptr : pos_bytes.data();
-    v.dense_ratio = args.dense_ratio;
-    v.doc_lo = args.doc_lo;
-    v.doc_hi = args.doc_hi;
-    v.positions = positions;
-    v.lean_wgs = lean_wgs;
-    v.lean_wgs_two = lean_wgs_two;
-    v.lean_wgs_ph = lean_wgs_ph;
-    v.gen_cap = gen_cap;
-    return v;
-  }
-};
-
-struct wsr_batch {
-  int max_q = 0, stride = 0, nq = 0;
-  gpu::DevBuf<uint8_t> d_qb;       // QueryIn[nq], then the term table of queries over kMaxTerms (bytes)
-  QueryIn* d_q() const { return reinterpret_cast<QueryIn*>(d_qb.get()); }
-  gpu::DevBuf<QueryPlan> d_plan;
-  gpu::DevBuf<QueryDesc> d_desc;   // lean queries' work records
-  gpu::DevBuf<PlanPart> d_part;    // plan pass 1 -> 2 partial sums, per kPlanThreads queries
-  gpu::DevBuf<uint32_t> d_ctr;
-  gpu::PinnedBuf<uint32_t> h_ctr;  // pinned host copy of the counters (fetch)
-  gpu::DevBuf<Event> d_events;
-  gpu::DevBuf<uint32_t> d_evcnt, d_itemq;   // per item: its events, its query (sized together with d_pub)
-  gpu::DevBuf<HitDev> d_hits;
-  gpu::DevBuf<int32_t> d_nhits;
-  gpu::DevBuf<uint32_t> d_qdone;   // fused replay: completed items per query
-  gpu::DevBuf<uint64_t> d_pub;     // per item score floor
-  gpu::DevBuf<uint32_t> d_stats;   // per general workgroup, then per lean wave: survivors, blocks
-  gpu::DevBuf<uint32_t> d_ph;      // phrase scratch, gen_cap * kPhraseScratch (lazily)
-  BatchClass cls;                // the uploaded queries' class flags, grids and OR counts (plan_upload)
-  Launches launched;             // the persistent kernels of the last run (their stats rows are its own)
-  uint32_t seg_cap = kSegCost;   // driver blocks per work item at most (wsr_batch_set_item_blocks)
-  // doc-range shard exchange (wsr_shard_step): per owner a region of {count,
-  // offset} pairs + an event slot, owner-major to send, shard-major received;
-  // allocated on first use
-  gpu::DevBuf<Event> d_xsend, d_xrecv;   // region events * pairs each
-  int x_pairs = 0;
-  gpu::Event xev[2];   // emission done -> comm stream; exchange done -> replay
-  std::atomic<bool> x_pending{false};   // a shard step's exchange + owner replay (xev[1]) not yet joined
-  // exchanges asked of the communicator's worker thread for this batch, and
-  // those it has enqueued (xev[1] recorded): xev[1] is only waited on once
-  // they agree (x_join)
-  std::atomic<uint64_t> x_req{0};
-  std::atomic<uint64_t> x_enq{0};
-  // a step group's owner replay of this batch deferred (wsr_shard_steps) and
-  // not yet enqueued: x_join has x_comm enqueue it first (atomic: a fetch on
-  // one thread may race a step group on another; the communicator's pend_mu
-  // orders what the two do with the group)
-  std::atomic<wsr_comm*> x_comm{nullptr};
-  bool x_fused = false;     // the last run emitted into the exchange regions (fill counters after d_ctr)
-  // a host-exchange owner replay of this batch waiting for another batch's
-  // run to carry it (wsr_shard_step_replay_deferred); its regions are in
-  // d_xrecv once xev[0] (recorded after their copy on st) has passed.  Set and
-  // cleared under the handle's hdef_mu; a run that takes it counts it in
-  // x_req before clearing it, so x_join waits for its enqueue
-  std::atomic<wsr_handle*> hdef{nullptr};
-  int32_t hdef_rank = 0;
-  int x_world = 0, x_qpr = 0;   // ... for this world and q_per_owner
-  int64_t x_slot = 0;           //     and slot (the replay half must match them)
-  // disjunctive (OR) queries: their table, items and event slots, allocated
-  // by the first upload that holds one (cls.n_or == 0: no extra launch)
-  gpu::DevBuf<OrQuery> d_orq;
-  gpu::DevBuf<OrItem> d_oritem;
-  gpu::DevBuf<uint32_t> d_orevcnt;   // (sized together with d_oritem)
-  gpu::DevBuf<Event> d_orev;
-  gpu::DevBuf<unsigned long long> d_orstat;   // kNumOrStats counters of the last run
-  gpu::Event ev[5];   // (timing events) [4]: lean kernel end
-  // Each batch runs on its own streams, so consecutive batches overlap on the
-  // device (one's plan and first items under the other's last items); the
-  // general kernel goes to st2, forked from and joined back into st.  HIP maps
-  // streams to its hardware queues (GPU_MAX_HW_QUEUES, 4) round-robin in
-  // creation order, and kernels of one queue run in order: a batch creates
-  // three streams (st_pad carries only the conjunctive lean kernel of batches
-  // with phrase queries, beside the other two), so the lean kernels of consecutive
-  // batches land on queues 3 apart, i.e. on all four in turn, instead of
-  // alternating between two (with two streams per batch the C3 headline fell
-  // from 21.7 to 18.9 M q/s and C2 from 35.0 to 29.6 M at unchanged per-batch
-  // kernel times, profiles/r04a_bench.json).
-  gpu::Stream st, st2, st_pad;   // (created in this order, wsr_batch_create; nothing relies on the order they go in)
-  gpu::Event fork, join, join_ph;
-  bool ran = false;
-};
-static void replay_flush(wsr_comm* c, const wsr_batch* upto);
-static void host_replay_flush(wsr_batch* b);
-// Is a shard step's exchange of b outstanding?  First wait until every
-// exchange and owner replay asked for b is enqueued (by the communicator's
-// worker, or, deferred, by a later step group or batch run: enqueued now if
-// still pending), so that xev[1] is the record to wait on.
-static bool x_join(wsr_batch* b) {
-  if (b->hdef) host_replay_flush(b);
-  if (wsr_comm* c = b->x_comm.load(std::memory_order_acquire)) replay_flush(c, b);
-  while (b->x_enq.load(std::memory_order_acquire) != b->x_req.load(std::memory_order_acquire))
-    std::this_thread::yield();
-  return b->x_pending;
-}
 
 namespace {
 // bytes dev_upload allocates for a host array (at least one element)
@@ -688,7 +513,7 @@ int wsr_batch_create(wsr_handle* h, int32_t max_q, int32_t stride, wsr_batch** o
 
 void wsr_batch_destroy(wsr_handle* h, wsr_batch* b) {
   if (!b) return;
-  if (x_join(b)) (void)hipEventSynchronize(b->xev[1]);   // a shard step's exchange reads its buffers
+  if (b->x.join()) (void)hipEventSynchronize(b->x.ev[1]);   // a shard step's exchange reads its buffers
   if (b->st) (void)hipStreamSynchronize(b->st);
   if (b->st2) (void)hipStreamSynchronize(b->st2);
   if (b->st_pad) (void)hipStreamSynchronize(b->st_pad);
@@ -716,7 +541,7 @@ int wsr_batch_upload(wsr_handle* h, wsr_batch* b, const wsr_query* q, int32_t nq
   try {
     HIP_OK(hipSetDevice(h->device));
     HIP_OK(hipStreamSynchronize(b->st));
-    if (x_join(b)) HIP_OK(hipEventSynchronize(b->xev[1]));   // a shard step's exchange + replay
+    if (b->x.join()) HIP_OK(hipEventSynchronize(b->x.ev[1]));   // a shard step's exchange + replay
     // (on-demand buffers: a failure leaves the buffer empty, so the next upload allocates again)
     b->d_events.reserve(p.ev_need, p.ev_need + p.ev_need / 4 + 4096);
     if (p.items_need > b->d_evcnt.size() || !b->d_evcnt)
@@ -747,24 +572,6 @@ int wsr_batch_upload(wsr_handle* h, wsr_batch* b, const wsr_query* q, int32_t nq
   b->ran = false;
   return WSR_OK;
 }
-
-// Shard emission of a batch run (wsr_shard_step): owners, queries per owner,
-// slot, and the send / meta buffers the segment kernels append to.
-struct ShardEmit {
-  int owners;
-  int32_t qpr;
-  uint64_t slot;         // capacity of an owner's slot (events)
-  Event* send;           // owner 0's slot; owner o's at send + o * stride
-  uint64_t stride;
-  int32_t* meta;         // owner 0's {count, offset} block; owner o's at meta + o * meta_stride
-  uint64_t meta_stride;
-};
-
-static int batch_run(wsr_handle* h, wsr_batch* b, const ShardEmit* se = nullptr, const OwnerJob* oj = nullptr);
-static wsr_batch* take_host_replay(wsr_handle* h, const wsr_batch* b, OwnerJob* oj);
-static void host_replay_enqueue(wsr_batch* pb, wsr_handle* h);
-
-
 int wsr_batch_run(wsr_handle* h, wsr_batch* b) { return batch_run(h, b); }
 
 // One run of the batch: plan, then the lean and general segment kernels on
@@ -780,10 +587,31 @@ int wsr_debug_fail_runs(int32_t n) {
   return WSR_OK;
 }
 
-static int batch_run(wsr_handle* h, wsr_batch* b, const ShardEmit* se, const OwnerJob* oj) {
+}  // extern "C"
+
+// What the kernels of a run of b do with a finished query: replay it into the
+// batch's hit rows, or (se: a shard step) emit it into the exchange regions;
+// oj: the owner replay the lean kernel's tail carries.
+static FusedReplay fused_replay_of(const wsr_batch* b, const EmitView* se, const OwnerJob* oj) {
+  FusedReplay fr{b->d_qdone, b->d_hits, b->stride, b->d_nhits};
+  if (se) {
+    fr.x_send = se->send;
+    fr.x_meta = se->meta;
+    fr.x_fill = b->d_ctr + kNumCounters;
+    fr.x_err = b->d_ctr + kCtrError;
+    fr.x_slot = se->slot;
+    fr.x_stride = se->stride;
+    fr.x_meta_stride = se->meta_stride;
+    fr.x_qpr = se->qpr;
+  }
+  if (oj) fr.oj = *oj;
+  return fr;
+}
+
+// (a shard step's callers have refused a batch with a disjunctive query: check_step, shard_exchange.cc)
+int batch_run(wsr_handle* h, wsr_batch* b, const EmitView* se, const OwnerJob* oj) {
   if (!h || !b) return fail(WSR_E_INVALID, "null argument");
   const BatchClass& c = b->cls;
-  if (se && c.has_or) return fail(WSR_E_INVALID, "a doc-range shard step cannot run a disjunctive query");
   for (int32_t f = g_fail_runs.load(); f > 0;)
     if (g_fail_runs.compare_exchange_weak(f, f - 1)) return fail(WSR_E_HIP, "injected run failure");
   wsr_batch* pb = nullptr;   // (a host replay taken, below)
@@ -793,29 +621,18 @@ static int batch_run(wsr_handle* h, wsr_batch* b, const ShardEmit* se, const Own
     hipStream_t st = b->st;
     // the previous shard step's exchange and owner replay (on the communicator's
     // stream) read this batch's buffers and write its results
-    if (x_join(b)) HIP_OK(hipStreamWaitEvent(st, b->xev[1], 0));
-    b->x_pending = false;
+    if (b->x.join()) HIP_OK(hipStreamWaitEvent(st, b->x.ev[1], 0));
+    b->x.pending = false;
     // a host-exchange owner replay another batch deferred (wsr_shard_step_
     // replay_deferred) rides in this run's lean kernel, after its regions'
     // copy; its end is recorded on this stream behind the lean kernel
     OwnerJob hoj{};
     if (!oj && (pb = take_host_replay(h, b, &hoj))) {
-      HIP_OK(hipStreamWaitEvent(st, pb->xev[0], 0));
+      HIP_OK(hipStreamWaitEvent(st, pb->x.ev[0], 0));
       oj = &hoj;
     }
     HIP_OK(hipMemsetAsync(b->d_ctr, 0, sizeof(uint32_t) * (kNumCounters + (se ? se->owners : 0)), st));
-    FusedReplay fr{b->d_qdone, b->d_hits, b->stride, b->d_nhits};
-    if (se) {
-      fr.x_send = se->send;
-      fr.x_meta = se->meta;
-      fr.x_fill = b->d_ctr + kNumCounters;
-      fr.x_err = b->d_ctr + kCtrError;
-      fr.x_slot = se->slot;
-      fr.x_stride = se->stride;
-      fr.x_meta_stride = se->meta_stride;
-      fr.x_qpr = se->qpr;
-    }
-    if (oj) fr.oj = *oj;
+    const FusedReplay fr = fused_replay_of(b, se, oj);
     HIP_OK(hipEventRecord(b->ev[0], st));
     IndexArgs pa = h->args;   // (the batch's item length)
     pa.seg_cap = b->seg_cap;
@@ -852,7 +669,7 @@ static int batch_run(wsr_handle* h, wsr_batch* b, const ShardEmit* se, const Own
                            c.lean_wgs, fr, b->d_itemq, b->d_pub, b->d_desc, false, c.two_conj, c.one_conj,
                            b->st_pad));
       if (pb) {   // the replay's end: behind the conjunctive launch that carried it
-        HIP_OK(hipEventRecord(pb->xev[1], b->st_pad));
+        HIP_OK(hipEventRecord(pb->x.ev[1], b->st_pad));
         pb_queued = true;
       }
       HIP_OK(hipEventRecord(b->join_ph, b->st_pad));
@@ -867,12 +684,11 @@ static int batch_run(wsr_handle* h, wsr_batch* b, const ShardEmit* se, const Own
     }
     HIP_OK(hipEventRecord(b->ev[4], st));
     if (pb && !pb_queued) {
-      HIP_OK(hipEventRecord(pb->xev[1], st));
+      HIP_OK(hipEventRecord(pb->x.ev[1], st));
       pb_queued = true;
     }
     if (pb) {
-      pb->x_pending = true;
-      pb->x_enq.fetch_add(1, std::memory_order_release);   // (take_host_replay counted it in x_req)
+      pb->x.enqueued(true, false);   // (take_host_replay counted it in req)
       pb = nullptr;
     }
     HIP_OK(hipStreamWaitEvent(st, b->join, 0));
@@ -891,17 +707,15 @@ static int batch_run(wsr_handle* h, wsr_batch* b, const ShardEmit* se, const Own
     }
     HIP_OK(hipEventRecord(b->ev[3], st));
   } catch (const std::exception& e) {
-    if (pb) {
-      if (!pb_queued) host_replay_enqueue(pb, h);   // (its own stream, then)
-      else pb->x_pending = true;
-      pb->x_enq.fetch_add(1, std::memory_order_release);
-    }
+    if (pb) pb->x.enqueued(pb_queued || host_replay_enqueue(pb, h), false);   // (not queued: its own stream, then)
     return fail(WSR_E_HIP, e.what());
   }
   b->ran = true;
-  b->x_fused = se != nullptr;
+  b->x.fused = se != nullptr;
   return WSR_OK;
 }
+
+extern "C" {
 
 int wsr_sync(wsr_handle* h) {
   if (!h) return fail(WSR_E_INVALID, "null argument");
@@ -932,7 +746,7 @@ static int batch_fetch(wsr_handle* h, wsr_batch* b, wsr_hit* hits, int32_t* n_hi
   try {
     HIP_OK(hipSetDevice(h->device));
     hipStream_t st = b->st;
-    if (x_join(b)) HIP_OK(hipStreamWaitEvent(st, b->xev[1], 0));   // a shard step's exchange + replay
+    if (b->x.join()) HIP_OK(hipStreamWaitEvent(st, b->x.ev[1], 0));   // a shard step's exchange + replay
     HIP_OK(hipMemcpyAsync(b->h_ctr, b->d_ctr, sizeof(uint32_t) * kNumCounters, hipMemcpyDeviceToHost, st));
     if (b->nq && !(host_pinned(hits) && host_pinned(n_hits))) {
       // pageable destinations: a queued copy into them is staged by the runtime
@@ -995,7 +809,7 @@ int wsr_batch_ready(wsr_handle* h, wsr_batch* b) {
   if (!h || !b) return fail(WSR_E_INVALID, "null argument");
   if (!b->ran) return 0;
   hipError_t e = hipEventQuery(b->ev[3]);   // recorded after the batch's last kernel
-  if (e == hipSuccess && x_join(b)) e = hipEventQuery(b->xev[1]);   // and a shard step's replay
+  if (e == hipSuccess && b->x.join()) e = hipEventQuery(b->x.ev[1]);   // and a shard step's replay
   if (e == hipSuccess) return 1;
   if (e == hipErrorNotReady) return 0;
   return fail(WSR_E_HIP, hipGetErrorString(e));
@@ -1006,7 +820,7 @@ int wsr_batch_stats_get(wsr_handle* h, wsr_batch* b, wsr_batch_stats* out) {
   std::lock_guard<std::mutex> g(h->mu);
   try {
     HIP_OK(hipStreamSynchronize(b->st));
-    if (x_join(b)) HIP_OK(hipEventSynchronize(b->xev[1]));   // a shard step's exchange + replay
+    if (b->x.join()) HIP_OK(hipEventSynchronize(b->x.ev[1]));   // a shard step's exchange + replay
     uint32_t ctr[kNumCounters];
     HIP_OK(hipMemcpy(ctr, b->d_ctr, sizeof ctr, hipMemcpyDeviceToHost));
     const int rows = b->cls.seg_grid + kLeanWaves * (b->cls.lean_wgs + (b->cls.has_phrase ? b->cls.lean_wgs_ph : 0));
@@ -1209,12 +1023,12 @@ int wsr_class_order(const wsr_query* q, int32_t nq, int32_t* order, int32_t* n_c
 }
 
 int wsr_shard_fill(wsr_handle* h, wsr_batch* b, int32_t n_owners, int64_t* owner_totals) {
-  if (!h || !b || !b->x_fused || !owner_totals || n_owners <= 0 || n_owners > b->x_world)
+  if (!h || !b || !b->x.fused || !owner_totals || n_owners <= 0 || n_owners > b->x.world)
     return fail(WSR_E_INVALID, "call wsr_shard_step (or wsr_shard_step_emit) first");
   try {
     HIP_OK(hipSetDevice(h->device));
     HIP_OK(hipStreamSynchronize(b->st));
-    if (x_join(b)) HIP_OK(hipEventSynchronize(b->xev[1]));   // a shard step's exchange + replay
+    if (b->x.join()) HIP_OK(hipEventSynchronize(b->x.ev[1]));   // a shard step's exchange + replay
     // the segment kernels' per-owner fill counters
     std::vector<uint32_t> fill(n_owners);
     HIP_OK(hipMemcpy(fill.data(), b->d_ctr + kNumCounters, sizeof(uint32_t) * n_owners, hipMemcpyDeviceToHost));
@@ -1231,701 +1045,6 @@ int wsr_batch_stream(wsr_handle* h, wsr_batch* b, void** stream) {
   return WSR_OK;
 }
 
-// ---- native RCCL exchange (one process per GPU, no Python in the loop) ----
-// Every collective of a communicator runs on its one stream, in issue order
-// (the same order on every rank), whatever batch stream it serves: a step's
-// pack is joined into it by an event and its replay waits for it by another,
-// so consecutive batches still overlap their kernels.
-// The exchange half of a step group (the collective and the owner replays)
-// is enqueued by the communicator's own worker thread: an ncclAllToAll call
-// can hold its caller for milliseconds while the device is busy (RCCL's host
-// side waits for its earlier work: 0.13-0.23 ms of host time per step in the
-// hybrid rehearsal, the loop host-bound, profiles/r04g/), and the caller's
-// next batches must not wait behind it.  Jobs run in submission order, so
-// every rank issues its collectives in the same order.
-//
-// A group's owner replays are deferred (WSR_REPLAY_DEFER, default 1) into the
-// lean kernels of the step group kReplayLag groups later: each of its
-// batches' lean kernel, its own items done, replays one batch of the earlier
-// group (OwnerJob).  A separate owner replay launch -- thousands of one-wave,
-// latency-bound workgroups per batch beside the persistent lean kernels --
-// cost more than its work (one-rank rehearsal 16.8 M q/s with it, 20.9 M with
-// the replay dropped, profiles/r04r/).  Whatever needs a deferred replay's
-// results first (a fetch, the batch's next run, wsr_comm_flush) enqueues it
-// on the communicator's stream instead (replay_flush).
-struct XGroup {
-  wsr_handle* h;
-  std::vector<wsr_batch*> bs;
-  int32_t qpr;
-  int64_t slot;
-  int xs;                              // its exchange buffers: c->xs[xs]
-  bool defer;
-  std::vector<hipEvent_t> wait_done;   // the slot's previous replays (before the all-to-all)
-  std::vector<uint8_t> queued;         // deferred: bs[i]'s replay enqueued
-  std::atomic<bool> enq{false};        // the worker has enqueued the all-to-all (and, not deferred, the replays)
-};
-using XJob = std::shared_ptr<XGroup>;
-constexpr int kXSlots = 4;       // exchange buffer sets in rotation
-constexpr size_t kReplayLag = 2;  // groups between a group's exchange and its deferred replays
-struct XSlot {
-  gpu::DevBuf<Event> send, recv;
-  gpu::Event xa;                      // the last all-to-all out of this slot done (comm stream)
-  std::vector<gpu::Event> done;       // its group's owner replays done, one per batch
-  size_t n_done = 0;                  // (recorded)
-  std::shared_ptr<XGroup> last;       // the group that used it last
-};
-// Loopback group (wsr_loopback_create): the all-to-all of W communicators of
-// one process by device copies.  Call n of every rank meets in calls[n]:
-// each rank records its send buffer ready, waits on the host until all W have
-// (phase 1), copies region r of every rank's send buffer into slot g of its
-// receive buffer behind that rank's ready event, records its reads done and
-// waits until all W have (phase 2), then makes its stream wait for every
-// rank's reads -- so a rank's collective completes only once its send buffer
-// has been read by all, as ncclAllToAll's does, and no rank records its
-// per-communicator events again before every rank has waited on them.
-struct wsr_loopback {
-  int world = 0;
-  std::mutex mu;
-  std::condition_variable cv;
-  struct Call {
-    std::vector<const void*> send;
-    std::vector<hipEvent_t> ready, read;
-    int arrived = 0, read_done = 0, left = 0;
-  };
-  std::map<uint64_t, Call> calls;
-};
-
-struct wsr_comm {
-  ncclComm_t comm = nullptr;
-  wsr_loopback* loop = nullptr;   // a loopback communicator (no RCCL)
-  uint64_t loop_seq = 0;
-  gpu::Event loop_ready, loop_read;
-  gpu::Stream stream;
-  int world = 0, rank = 0, device = 0;
-  // WSR_HOST_TIMING=1: host time per phase of wsr_shard_step (enqueue only),
-  // printed to stderr when the communicator closes
-  bool timing = false;
-  uint64_t steps = 0, t_ns[4] = {0, 0, 0, 0};   // run, submit, rccl (worker), replay (worker)
-  std::thread worker;
-  std::mutex mu;
-  std::condition_variable cv;
-  std::vector<XJob> jobs;   // (FIFO)
-  size_t head = 0;
-  bool stop = false;
-  std::atomic<int> err{WSR_OK};   // the worker's first failure, reported by the next call
-  std::string err_msg;
-  XSlot xs[kXSlots];
-  uint64_t n_groups = 0;
-  std::atomic<int64_t> replays_lean{0}, replays_stream{0};   // wsr_comm_stats
-  bool defer = true;
-  // deferred groups, oldest first.  pend, XGroup::queued and the batches'
-  // x_comm are changed by wsr_shard_steps and by whatever flushes a deferred
-  // replay (x_join inside a fetch, upload, run or destroy; wsr_comm_flush),
-  // which may run on other threads: pend_mu orders them (recursive: a step
-  // group flushes its own batches' earlier replays).
-  std::deque<std::shared_ptr<XGroup>> pend;
-  std::recursive_mutex pend_mu;
-};
-
-static void set_comm_err(wsr_comm* c, int rc, const std::string& msg) {
-  std::lock_guard<std::mutex> g(c->mu);
-  if (c->err.load() == WSR_OK) {
-    c->err_msg = msg;
-    c->err.store(rc);
-  }
-}
-
-static uint64_t now_ns() {
-  return static_cast<uint64_t>(std::chrono::duration_cast<std::chrono::nanoseconds>(
-                                   std::chrono::steady_clock::now().time_since_epoch())
-                                   .count());
-}
-
-static int step_replay_from(wsr_handle* h, wsr_batch* b, int rank, int W, int32_t q_per_owner, const Event* recv,
-                            uint64_t owner_stride, hipStream_t st);
-
-// The loopback group's all-to-all (wsr_loopback above): bytes per rank pair.
-static void loopback_alltoall(wsr_comm* c, const Event* send, Event* recv, uint64_t bytes) {
-  wsr_loopback* L = c->loop;
-  const int W = L->world, r = c->rank;
-  HIP_OK(hipEventRecord(c->loop_ready, c->stream));
-  const uint64_t n = c->loop_seq++;
-  wsr_loopback::Call* call;
-  {
-    std::unique_lock<std::mutex> lk(L->mu);
-    call = &L->calls[n];
-    if (call->send.empty()) {
-      call->send.assign(W, nullptr);
-      call->ready.assign(W, nullptr);
-      call->read.assign(W, nullptr);
-    }
-    call->send[r] = send;
-    call->ready[r] = c->loop_ready;
-    ++call->arrived;
-    L->cv.notify_all();
-    L->cv.wait(lk, [&] { return call->arrived == W; });
-  }
-  const uint8_t* src_base = nullptr;
-  for (int g = 0; g < W; ++g) {
-    HIP_OK(hipStreamWaitEvent(c->stream, call->ready[g], 0));
-    src_base = static_cast<const uint8_t*>(call->send[g]);
-    HIP_OK(hipMemcpyAsync(reinterpret_cast<uint8_t*>(recv) + g * bytes, src_base + r * bytes, bytes,
-                          hipMemcpyDeviceToDevice, c->stream));
-  }
-  HIP_OK(hipEventRecord(c->loop_read, c->stream));
-  {
-    std::unique_lock<std::mutex> lk(L->mu);
-    call->read[r] = c->loop_read;
-    ++call->read_done;
-    L->cv.notify_all();
-    L->cv.wait(lk, [&] { return call->read_done == W; });
-  }
-  for (int g = 0; g < W; ++g) HIP_OK(hipStreamWaitEvent(c->stream, call->read[g], 0));
-  {
-    std::lock_guard<std::mutex> lk(L->mu);
-    if (++call->left == W) L->calls.erase(n);
-  }
-}
-
-// One job: wait for the group's emissions (and for the slot's previous
-// replays), one ncclAllToAll of the owners' runs of regions, then -- not
-// deferred -- the owner replays and the end event of every batch.
-static void run_xjob(wsr_comm* c, const XJob& jp) {
-  XGroup& j = *jp;
-  XSlot& S = c->xs[j.xs];
-  const int W = c->world;
-  const uint64_t region = (static_cast<uint64_t>(j.qpr) + 1) / 2 + static_cast<uint64_t>(j.slot);
-  const uint64_t run = region * j.bs.size();
-  uint64_t t0 = c->timing ? now_ns() : 0;
-  int rc = WSR_OK;
-  std::string msg;
-  try {
-    HIP_OK(hipSetDevice(c->device));
-    // (the device waits for the emissions, not this thread: waiting on the
-    // host first makes the collective's own call short, 2-8 us, but the loop
-    // no faster -- the enqueueing thread is held by full hardware queues
-    // either way, and the exchange starts later: 16.8 -> 15.3 M q/s every
-    // query sharded, profiles/r04t/)
-    for (wsr_batch* b : j.bs) HIP_OK(hipStreamWaitEvent(c->stream, b->xev[0], 0));
-    for (hipEvent_t e : j.wait_done) HIP_OK(hipStreamWaitEvent(c->stream, e, 0));
-    if (c->loop) {
-      loopback_alltoall(c, S.send, S.recv, run * sizeof(Event));
-    } else {
-      const ncclResult_t r = ncclAllToAll(S.send, S.recv, run * (sizeof(Event) / sizeof(uint64_t)),
-                                          ncclUint64, c->comm, c->stream);
-      if (r != ncclSuccess) throw std::runtime_error(std::string("ncclAllToAll: ") + ncclGetErrorString(r));
-    }
-    HIP_OK(hipEventRecord(S.xa, c->stream));
-  } catch (const std::exception& e) {
-    rc = WSR_E_HIP;
-    msg = e.what();
-  }
-  uint64_t t1 = c->timing ? now_ns() : 0;
-  if (!j.defer) {
-    for (size_t i = 0; i < j.bs.size() && rc == WSR_OK; ++i) {
-      rc = step_replay_from(j.h, j.bs[i], c->rank, W, j.qpr, S.recv + region * i, run, c->stream);
-      if (rc) msg = g_err;
-      else if (hipEventRecord(j.bs[i]->xev[1], c->stream) != hipSuccess ||
-               hipEventRecord(S.done[i], c->stream) != hipSuccess) {
-        rc = WSR_E_HIP;
-        msg = "hipEventRecord failed";
-      }
-    }
-    for (wsr_batch* b : j.bs) {
-      b->x_pending = rc == WSR_OK;
-      b->x_enq.fetch_add(1, std::memory_order_release);
-    }
-    c->replays_stream.fetch_add(static_cast<int64_t>(j.bs.size()));
-  }
-  if (rc != WSR_OK) set_comm_err(c, rc, msg);
-  j.enq.store(true, std::memory_order_release);
-  if (c->timing) {
-    const uint64_t t2 = now_ns();
-    c->t_ns[2] += t1 - t0;
-    c->t_ns[3] += t2 - t1;
-  }
-}
-
-static void exchange_worker(wsr_comm* c) {
-  for (;;) {
-    XJob j;
-    {
-      std::unique_lock<std::mutex> lk(c->mu);
-      c->cv.wait(lk, [&] { return c->stop || c->head < c->jobs.size(); });
-      if (c->head == c->jobs.size()) return;   // (stop, and drained)
-      j = std::move(c->jobs[c->head++]);
-      if (c->head == c->jobs.size()) {
-        c->jobs.clear();
-        c->head = 0;
-      }
-    }
-    run_xjob(c, j);
-  }
-}
-
-int wsr_comm_unique_id(uint8_t* id) {
-  if (!id) return fail(WSR_E_INVALID, "null argument");
-  ncclUniqueId u;
-  const ncclResult_t r = ncclGetUniqueId(&u);
-  if (r != ncclSuccess) return fail(WSR_E_HIP, std::string("ncclGetUniqueId: ") + ncclGetErrorString(r));
-  static_assert(sizeof(ncclUniqueId) == WSR_COMM_ID_BYTES, "RCCL unique id size");
-  std::memcpy(id, &u, sizeof u);
-  return WSR_OK;
-}
-
-int wsr_comm_open(const uint8_t* id, int32_t world, int32_t rank, int32_t device, wsr_comm** out) {
-  if (!id || !out || world < 1 || rank < 0 || rank >= world) return fail(WSR_E_INVALID, "bad comm arguments");
-  *out = nullptr;
-  if (hipSetDevice(device) != hipSuccess) return fail(WSR_E_HIP, "hipSetDevice failed");
-  std::unique_ptr<wsr_comm> c(new wsr_comm());
-  ncclUniqueId u;
-  std::memcpy(&u, id, sizeof u);
-  const ncclResult_t r = ncclCommInitRank(&c->comm, world, u, rank);
-  if (r != ncclSuccess) return fail(WSR_E_HIP, std::string("ncclCommInitRank: ") + ncclGetErrorString(r));
-  // exchange stream priority (WSR_COMM_PRIORITY=1: high).  Normal since
-  // round 4: at high priority the owner replays' thousands of one-wave
-  // workgroups are dispatched ahead of the next batches' persistent kernels;
-  // one-rank rehearsal 15.6 -> 16.7 M q/s every query sharded, 12.7 -> 15.4 M
-  // hybrid (profiles/r04g/; round 2 had measured +3 % for high)
-  // (a stream with a full CU mask, i.e. a hardware queue of its own at normal
-  // priority, was slower again: 16.5 / 14.2 M against 17.0 / 15.6 M,
-  // profiles/r04n/; low priority was slower still: 16.3 / 12.9 M against
-  // 16.7 / 15.3 M, profiles/r04s/)
-  int lo_prio = 0, hi_prio = 0;
-  const bool prio = env_number("WSR_COMM_PRIORITY", 0) != 0 &&
-                    hipDeviceGetStreamPriorityRange(&lo_prio, &hi_prio) == hipSuccess;
-  try {
-    c->stream = gpu::make_stream(prio ? &hi_prio : nullptr);
-  } catch (const std::exception& e) {
-    (void)ncclCommDestroy(c->comm);
-    return fail(WSR_E_HIP, e.what());
-  }
-  c->world = world;
-  c->rank = rank;
-  c->device = device;
-  const char* ht = std::getenv("WSR_HOST_TIMING");
-  c->timing = ht && *ht && *ht != '0';
-  c->defer = env_number("WSR_REPLAY_DEFER", 1) != 0;
-  wsr_comm* cp = c.get();
-  cp->worker = std::thread([cp] { exchange_worker(cp); });
-  *out = c.release();
-  return WSR_OK;
-}
-
-int wsr_loopback_create(int32_t world, wsr_loopback** out) {
-  if (!out || world < 1 || world > kMaxOwners) return fail(WSR_E_INVALID, "bad loopback arguments");
-  *out = new wsr_loopback();
-  (*out)->world = world;
-  return WSR_OK;
-}
-
-void wsr_loopback_destroy(wsr_loopback* l) { delete l; }
-
-int wsr_comm_open_loopback(wsr_loopback* l, int32_t rank, int32_t device, wsr_comm** out) {
-  if (!l || !out || rank < 0 || rank >= l->world) return fail(WSR_E_INVALID, "bad loopback comm arguments");
-  *out = nullptr;
-  if (hipSetDevice(device) != hipSuccess) return fail(WSR_E_HIP, "hipSetDevice failed");
-  std::unique_ptr<wsr_comm> c(new wsr_comm());
-  c->loop = l;
-  try {
-    c->stream = gpu::make_stream();
-    c->loop_ready = gpu::make_event();
-    c->loop_read = gpu::make_event();
-  } catch (const std::exception& e) {
-    return fail(WSR_E_HIP, e.what());
-  }
-  c->world = l->world;
-  c->rank = rank;
-  c->device = device;
-  c->defer = env_number("WSR_REPLAY_DEFER", 1) != 0;
-  wsr_comm* cp = c.get();
-  cp->worker = std::thread([cp] { exchange_worker(cp); });
-  *out = c.release();
-  return WSR_OK;
-}
-
-void wsr_comm_close(wsr_comm* c) {
-  if (!c) return;
-  (void)wsr_comm_flush(c);   // (every deferred replay enqueued before the worker stops)
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    c->stop = true;
-  }
-  c->cv.notify_one();
-  if (c->worker.joinable()) c->worker.join();
-  if (c->timing && c->steps)
-    std::fprintf(stderr, "wsr_shard_step host us/step over %llu steps: run %.1f submit %.1f rccl %.1f replay %.1f "
-                 "(rccl and replay: the exchange worker)\n",
-                 static_cast<unsigned long long>(c->steps), c->t_ns[0] / 1e3 / c->steps,
-                 c->t_ns[1] / 1e3 / c->steps, c->t_ns[2] / 1e3 / c->steps, c->t_ns[3] / 1e3 / c->steps);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
-  for (XSlot& S : c->xs)
-    for (size_t i = 0; i < S.n_done; ++i) (void)hipEventSynchronize(S.done[i]);   // (replays in lean kernels)
-  if (c->comm) (void)ncclCommDestroy(c->comm);   // (ahead of its stream, which goes with c)
-  delete c;
-}
-
-static int owner_replay_meta_on(wsr_handle* h, wsr_batch* b, int32_t q0, int32_t nq_owned, int32_t n_shards,
-                                const int32_t* d_rmeta, uint64_t meta_stride, uint64_t stride,
-                                const void* d_recv, hipStream_t st) {
-  if (!h || !b || n_shards <= 0 || n_shards > kMaxOwners || nq_owned < 0 || q0 < 0 || q0 + nq_owned > b->nq ||
-      stride == 0 || (nq_owned && (!d_rmeta || !d_recv)))
-    return fail(WSR_E_INVALID, "bad owner_replay_meta arguments");
-  try {
-    HIP_OK(hipSetDevice(h->device));
-    HIP_OK(launch_owner_replay_meta(b->d_q(), q0, nq_owned, n_shards, d_rmeta, meta_stride, stride,
-                                    static_cast<const Event*>(d_recv), b->d_hits, b->stride, b->d_nhits,
-                                    b->d_ctr, b->cls.has_wide, st));
-  } catch (const std::exception& e) {
-    return fail(WSR_E_HIP, e.what());
-  }
-  return WSR_OK;
-}
-
-// One step of a doc-range sharded batch, all of it enqueued, nothing waited on:
-//   batch stream: the plan + segment kernels; the worker that finishes a
-//     query reduces its events into the owner's region of the send buffer;
-//   communicator stream (joined by xev[0]): one ncclAllToAll of the regions
-//     (RCCL's pairwise exchange over xGMI), then the owner replay of this
-//     rank's queries; xev[1] marks the end.
-// An owner's region is [{count, offset} of its qpr queries, padded to whole
-// events][slot of events], so one collective moves both.  The batch stream
-// never waits on the exchange inside a step, so the next batches' kernels run
-// under it; the next run of this batch waits for xev[1] (long past by then),
-// and the fetches join it.
-// An owner's region: the meta block (2 int32 per query, 4 per event, so the
-// qpr pairs take ceil(qpr / 2) events) followed by the slot.
-static uint64_t region_events_of(int32_t q_per_owner, int64_t slot) {
-  return (static_cast<uint64_t>(q_per_owner) + 1) / 2 + static_cast<uint64_t>(slot);
-}
-
-static int check_step(wsr_handle* h, wsr_batch* b, int W, int32_t q_per_owner, int64_t slot) {
-  if (!h || !b || W < 1 || q_per_owner <= 0 || slot <= 0 || static_cast<int64_t>(q_per_owner) * W != b->nq)
-    return fail(WSR_E_INVALID, "bad shard_step arguments (the batch must hold world * q_per_owner queries)");
-  if (b->cls.has_or) return fail(WSR_E_INVALID, "a doc-range shard step cannot run a disjunctive query");
-  if (W > kMaxOwners) return fail(WSR_E_LIMIT, "more than kMaxOwners ranks");
-  if (static_cast<uint64_t>(slot) > 0xFFFFFFFFull) return fail(WSR_E_LIMIT, "slot over 2^32 events");
-  return WSR_OK;
-}
-
-// The events that order a shard step's exchange against the batch's runs.
-static void ensure_xev(wsr_batch* b) {
-  for (auto& e : b->xev) if (!e) e = gpu::make_event();
-}
-
-// The exchange buffers of b: send and receive, need events each.
-static void ensure_xbuf(wsr_batch* b, uint64_t need, int W) {
-  if (need > b->d_xsend.size() || W != b->x_pairs) {
-    if (x_join(b)) HIP_OK(hipEventSynchronize(b->xev[1]));
-    gpu::alloc_group(need, b->d_xsend, b->d_xrecv);
-    b->x_pairs = W;
-  }
-  ensure_xev(b);
-}
-
-// First half of a shard step: run the batch with fused emission into the
-// send regions, owner o's region at send + o * owner_stride events (one
-// batch: its own buffer, owner_stride = region; a step group: the group's
-// buffer, this batch's region within every owner's run of regions).
-static int step_emit_into(wsr_handle* h, wsr_batch* b, int W, int32_t q_per_owner, int64_t slot, Event* send,
-                          uint64_t owner_stride, const OwnerJob* oj = nullptr) {
-  const uint64_t meta_events = (static_cast<uint64_t>(q_per_owner) + 1) / 2;
-  const uint64_t meta_stride = owner_stride * (sizeof(Event) / sizeof(int32_t));   // int32 per owner
-  const ShardEmit se{W, q_per_owner, static_cast<uint64_t>(slot), send + meta_events, owner_stride,
-                     reinterpret_cast<int32_t*>(send), meta_stride};
-  const int rc = batch_run(h, b, &se, oj);
-  if (rc == WSR_OK) {
-    b->x_world = W;
-    b->x_qpr = q_per_owner;
-    b->x_slot = slot;
-  }
-  return rc;
-}
-
-static int step_emit(wsr_handle* h, wsr_batch* b, int W, int32_t q_per_owner, int64_t slot) {
-  if (int rc = check_step(h, b, W, q_per_owner, slot)) return rc;
-  const uint64_t region = region_events_of(q_per_owner, slot);
-  try {
-    HIP_OK(hipSetDevice(h->device));
-    ensure_xbuf(b, region * W, W);
-  } catch (const std::exception& e) {
-    return fail(WSR_E_HIP, e.what());
-  }
-  return step_emit_into(h, b, W, q_per_owner, slot, b->d_xsend, region);
-}
-
-// Second half: the owner replay of this rank's queries over the receive
-// regions (region g = what shard g sent this owner, at recv + g *
-// owner_stride events), on stream st.
-static int step_replay_from(wsr_handle* h, wsr_batch* b, int rank, int W, int32_t q_per_owner, const Event* recv,
-                            uint64_t owner_stride, hipStream_t st) {
-  const uint64_t meta_events = (static_cast<uint64_t>(q_per_owner) + 1) / 2;
-  const uint64_t meta_stride = owner_stride * (sizeof(Event) / sizeof(int32_t));
-  return owner_replay_meta_on(h, b, rank * q_per_owner, q_per_owner, W, reinterpret_cast<const int32_t*>(recv),
-                              meta_stride, owner_stride, recv + meta_events, st);
-}
-
-static int step_replay(wsr_handle* h, wsr_batch* b, int rank, int W, int32_t q_per_owner, int64_t slot,
-                       hipStream_t st) {
-  return step_replay_from(h, b, rank, W, q_per_owner, b->d_xrecv, region_events_of(q_per_owner, slot), st);
-}
-
-// A deferred group's replays not yet enqueued go to the communicator's
-// stream (after its all-to-all, which the worker has enqueued first).
-static void flush_group(wsr_comm* c, XGroup& g) {
-  while (!g.enq.load(std::memory_order_acquire)) std::this_thread::yield();
-  XSlot& S = c->xs[g.xs];
-  const uint64_t region = region_events_of(g.qpr, g.slot), run = region * g.bs.size();
-  int rc = c->err.load() == WSR_OK ? WSR_OK : WSR_E_HIP;
-  for (size_t i = 0; i < g.bs.size(); ++i) {
-    if (g.queued[i]) continue;
-    g.queued[i] = 1;
-    c->replays_stream.fetch_add(1);
-    wsr_batch* b = g.bs[i];
-    if (rc == WSR_OK) {
-      rc = step_replay_from(g.h, b, c->rank, c->world, g.qpr, S.recv + region * i, run, c->stream);
-      if (rc) set_comm_err(c, rc, g_err);
-      else if (hipEventRecord(b->xev[1], c->stream) != hipSuccess ||
-               hipEventRecord(S.done[i], c->stream) != hipSuccess) {
-        rc = WSR_E_HIP;
-        set_comm_err(c, rc, "hipEventRecord failed");
-      }
-    }
-    b->x_pending = rc == WSR_OK;
-    b->x_comm.store(nullptr, std::memory_order_release);
-    b->x_enq.fetch_add(1, std::memory_order_release);
-  }
-  S.n_done = g.bs.size();
-}
-
-// Enqueue the deferred replays of every pending group up to the one holding
-// `upto` (all of them: upto null), oldest first.
-static void replay_flush(wsr_comm* c, const wsr_batch* upto) {
-  std::lock_guard<std::recursive_mutex> lk(c->pend_mu);
-  if (upto) {
-    bool held = false;
-    for (const auto& g : c->pend)
-      for (size_t i = 0; i < g->bs.size(); ++i) held = held || (!g->queued[i] && g->bs[i] == upto);
-    if (!held) return;
-  }
-  while (!c->pend.empty()) {
-    std::shared_ptr<XGroup> g = c->pend.front();
-    c->pend.pop_front();
-    bool has = false;
-    for (size_t i = 0; i < g->bs.size(); ++i) has = has || (!g->queued[i] && g->bs[i] == upto);
-    flush_group(c, *g);
-    if (has) return;
-  }
-}
-
-int wsr_comm_flush(wsr_comm* c) {
-  if (!c) return fail(WSR_E_INVALID, "null argument");
-  try {
-    HIP_OK(hipSetDevice(c->device));
-    replay_flush(c, nullptr);
-  } catch (const std::exception& e) {
-    return fail(WSR_E_HIP, e.what());
-  }
-  if (const int e = c->err.load()) {
-    std::lock_guard<std::mutex> g(c->mu);
-    return fail(e, "exchange: " + c->err_msg);
-  }
-  return WSR_OK;
-}
-
-int wsr_comm_stats_get(wsr_comm* c, wsr_comm_stats* out) {
-  if (!c || !out) return fail(WSR_E_INVALID, "null argument");
-  std::lock_guard<std::recursive_mutex> lk(c->pend_mu);
-  out->groups = static_cast<int64_t>(c->n_groups);
-  out->steps = static_cast<int64_t>(c->steps);
-  out->replays_in_lean = c->replays_lean.load();
-  out->replays_on_stream = c->replays_stream.load();
-  return WSR_OK;
-}
-
-// A step group: n batches of the same shape, each emitted into its region of
-// every owner's run of n regions in one of the communicator's exchange buffer
-// sets, then ONE ncclAllToAll of the runs on the communicator's stream.  The
-// collective's host cost (~0.1-0.2 ms a call under load, more than a whole
-// step's kernels) is paid once per group.  The group's owner replays run on
-// the communicator's stream too, or (deferred, the default) in the lean
-// kernels of the group kReplayLag groups later: batch i of this group replays
-// batch i of that one after its own items.
-int wsr_shard_steps(wsr_handle* h, wsr_batch* const* bs, int32_t n, wsr_comm* c, int32_t q_per_owner,
-                    int64_t slot) {
-  if (!c || !bs || n < 1) return fail(WSR_E_INVALID, "bad shard_steps arguments");
-  if (const int e = c->err.load()) {   // an earlier exchange of this communicator failed
-    std::lock_guard<std::mutex> g(c->mu);
-    return fail(e, "exchange worker: " + c->err_msg);
-  }
-  const int W = c->world;
-  for (int i = 0; i < n; ++i) {
-    if (int rc = check_step(h, bs[i], W, q_per_owner, slot)) return rc;
-    for (int j = 0; j < i; ++j)
-      if (bs[j] == bs[i]) return fail(WSR_E_INVALID, "a batch twice in one step group");
-  }
-  uint64_t t0 = c->timing ? now_ns() : 0;
-  auto lap = [&](int i) {
-    if (!c->timing) return;
-    const uint64_t t = now_ns();
-    c->t_ns[i] += t - t0;
-    t0 = t;
-  };
-  const uint64_t region = region_events_of(q_per_owner, slot);
-  const uint64_t run = region * static_cast<uint64_t>(n);   // events per owner
-  std::lock_guard<std::recursive_mutex> pend_lock(c->pend_mu);
-  const int xs = static_cast<int>(c->n_groups % kXSlots);
-  XSlot& S = c->xs[xs];
-  std::shared_ptr<XGroup> P;   // the group whose replays this one's lean kernels take
-  // Once P is off pend, every exit enqueues what its lean kernels did not
-  // take on the communicator's stream: on an early error return its batches
-  // would otherwise wait in x_join for replays nobody can find any more.
-  struct FlushRest {
-    wsr_comm* c;
-    std::shared_ptr<XGroup>& P;
-    ~FlushRest() {
-      if (P) flush_group(c, *P);
-    }
-  } flush_rest{c, P};
-  std::vector<OwnerJob> oj(static_cast<size_t>(n));
-  try {
-    HIP_OK(hipSetDevice(h->device));
-    // this group's batches: their own earlier replays enqueued first
-    for (int i = 0; i < n; ++i) {
-      ensure_xev(bs[i]);
-      if (bs[i]->x_comm.load(std::memory_order_acquire)) replay_flush(c, bs[i]);
-    }
-    // the slot: its previous group's all-to-all and replays enqueued (their
-    // end events are what this group's emission and exchange wait for)
-    if (S.last) {
-      for (size_t i = 0; i < S.last->queued.size(); ++i)
-        if (!S.last->queued[i]) replay_flush(c, S.last->bs[i]);
-      while (!S.last->enq.load(std::memory_order_acquire)) std::this_thread::yield();
-    }
-    const uint64_t need = run * static_cast<uint64_t>(W);
-    if (need > S.send.size()) {
-      if (S.last) {
-        HIP_OK(hipEventSynchronize(S.xa));
-        for (size_t i = 0; i < S.n_done; ++i) HIP_OK(hipEventSynchronize(S.done[i]));
-        S.last.reset();
-        S.n_done = 0;
-      }
-      gpu::alloc_group(need, S.send, S.recv);
-    }
-    if (!S.xa) S.xa = gpu::make_event();
-    while (S.done.size() < static_cast<size_t>(n)) S.done.push_back(gpu::make_event());
-    // the deferred replays this group's lean kernels take
-    if (c->defer && c->pend.size() >= kReplayLag) {
-      P = c->pend.front();
-      c->pend.pop_front();
-      while (!P->enq.load(std::memory_order_acquire)) std::this_thread::yield();
-      const XSlot& SP = c->xs[P->xs];
-      const uint64_t rP = region_events_of(P->qpr, P->slot), runP = rP * P->bs.size();
-      const uint64_t meta_events = (static_cast<uint64_t>(P->qpr) + 1) / 2;
-      for (size_t i = 0; i < P->bs.size() && i < static_cast<size_t>(n); ++i) {
-        const wsr_batch* pb = P->bs[i];
-        if (P->queued[i]) continue;
-        if (pb->cls.has_wide) continue;   // (the LDS heap: on the communicator's stream)
-        const Event* recv = SP.recv + rP * i;
-        oj[i] = OwnerJob{pb->d_q(), reinterpret_cast<const int32_t*>(recv), recv + meta_events, pb->d_hits,
-                         pb->d_nhits, pb->d_ctr, runP * (sizeof(Event) / sizeof(int32_t)), runP,
-                         c->rank * P->qpr, P->qpr, W, pb->stride};
-      }
-    }
-  } catch (const std::exception& e) {
-    return fail(WSR_E_HIP, e.what());
-  }
-  for (int i = 0; i < n; ++i) {
-    wsr_batch* b = bs[i];
-    const OwnerJob* job = oj[i].nq > 0 ? &oj[i] : nullptr;
-    try {
-      if (S.last) HIP_OK(hipStreamWaitEvent(b->st, S.xa, 0));   // the slot's last all-to-all read its send buffer
-      if (job) HIP_OK(hipStreamWaitEvent(b->st, c->xs[P->xs].xa, 0));
-    } catch (const std::exception& e) {
-      return fail(WSR_E_HIP, e.what());
-    }
-    if (int rc = step_emit_into(h, b, W, q_per_owner, slot, S.send + region * i, run, job)) return rc;
-    if (hipEventRecord(b->xev[0], b->st) != hipSuccess) return fail(WSR_E_HIP, "hipEventRecord failed");
-    if (job) {
-      wsr_batch* pb = P->bs[static_cast<size_t>(i)];
-      if (hipEventRecord(pb->xev[1], b->st) != hipSuccess ||
-          hipEventRecord(c->xs[P->xs].done[static_cast<size_t>(i)], b->st) != hipSuccess)
-        return fail(WSR_E_HIP, "hipEventRecord failed");
-      pb->x_pending = true;
-      pb->x_comm.store(nullptr, std::memory_order_release);
-      P->queued[static_cast<size_t>(i)] = 1;
-      c->replays_lean.fetch_add(1);
-      pb->x_enq.fetch_add(1, std::memory_order_release);
-    }
-  }
-  // the rest of P (more batches than this group, or wide ones): the
-  // communicator's stream
-  if (P) flush_group(c, *P);
-  P.reset();
-  lap(0);
-  // the exchange half: the communicator's worker thread enqueues it
-  auto g = std::make_shared<XGroup>();
-  g->h = h;
-  g->bs.assign(bs, bs + n);
-  g->qpr = q_per_owner;
-  g->slot = slot;
-  g->xs = xs;
-  g->defer = c->defer;
-  g->queued.assign(static_cast<size_t>(n), g->defer ? 0 : 1);
-  if (S.last) g->wait_done.assign(S.done.begin(), S.done.begin() + static_cast<std::ptrdiff_t>(S.n_done));
-  S.last = g;
-  S.n_done = 0;
-  ++c->n_groups;
-  {
-    std::lock_guard<std::mutex> lk(c->mu);
-    for (int i = 0; i < n; ++i) {
-      bs[i]->x_req.fetch_add(1, std::memory_order_acq_rel);
-      if (g->defer) bs[i]->x_comm.store(c, std::memory_order_release);
-    }
-    c->jobs.push_back(g);
-  }
-  if (g->defer) c->pend.push_back(g);
-  c->cv.notify_one();
-  lap(1);
-  c->steps += static_cast<uint64_t>(n);
-  return WSR_OK;
-}
-
-int wsr_shard_step(wsr_handle* h, wsr_batch* b, wsr_comm* c, int32_t q_per_owner, int64_t slot) {
-  return wsr_shard_steps(h, &b, 1, c, q_per_owner, slot);
-}
-
-int wsr_shard_step_regions(int32_t q_per_owner, int64_t slot, uint64_t* region_bytes) {
-  if (q_per_owner <= 0 || slot <= 0 || !region_bytes) return fail(WSR_E_INVALID, "bad arguments");
-  *region_bytes = region_events_of(q_per_owner, slot) * sizeof(Event);
-  return WSR_OK;
-}
-
-static int shard_step_emit(wsr_handle* h, wsr_batch* b, int32_t world, int32_t q_per_owner, int64_t slot,
-                           void* host_send, bool wait) {
-  if (!host_send) return fail(WSR_E_INVALID, "null host buffer");
-  const int rc = step_emit(h, b, world, q_per_owner, slot);
-  if (rc) return rc;
-  try {
-    HIP_OK(hipMemcpyAsync(host_send, b->d_xsend, sizeof(Event) * region_events_of(q_per_owner, slot) * world,
-                          hipMemcpyDeviceToHost, b->st));
-    if (wait) HIP_OK(hipStreamSynchronize(b->st));
-  } catch (const std::exception& e) {
-    return fail(WSR_E_HIP, e.what());
-  }
-  return WSR_OK;
-}
-
-int wsr_shard_step_emit(wsr_handle* h, wsr_batch* b, int32_t world, int32_t q_per_owner, int64_t slot,
-                        void* host_send) {
-  return shard_step_emit(h, b, world, q_per_owner, slot, host_send, true);
-}
-
-int wsr_shard_step_emit_async(wsr_handle* h, wsr_batch* b, int32_t world, int32_t q_per_owner, int64_t slot,
-                              void* host_send) {
-  return shard_step_emit(h, b, world, q_per_owner, slot, host_send, false);
-}
-
 int wsr_batch_set_item_blocks(wsr_handle* h, wsr_batch* b, int32_t blocks) {
   if (!h || !b || blocks < 1 || blocks > kSegCost) return fail(WSR_E_INVALID, "item blocks must be 1..63");
   b->seg_cap = static_cast<uint32_t>(blocks);
@@ -1938,108 +1057,13 @@ int wsr_batch_stream_sync(wsr_handle* h, wsr_batch* b) {
   return e == hipSuccess ? WSR_OK : fail(WSR_E_HIP, hipGetErrorString(e));
 }
 
-int wsr_shard_step_replay(wsr_handle* h, wsr_batch* b, int32_t rank, int32_t world, int32_t q_per_owner,
-                          int64_t slot, const void* host_recv) {
-  // (the regions are read at the strides the emission wrote them with: the
-  // arguments must be the ones of the preceding wsr_shard_step_emit)
-  if (!h || !b || !host_recv || world < 1 || rank < 0 || rank >= world || q_per_owner <= 0 || slot <= 0 ||
-      !b->x_fused || b->x_world != world || b->x_qpr != q_per_owner || b->x_slot != slot ||
-      static_cast<int64_t>(q_per_owner) * world != b->nq)
-    return fail(WSR_E_INVALID, "call wsr_shard_step_emit with the same world, q_per_owner and slot first");
-  if (b->cls.has_or) return fail(WSR_E_INVALID, "a doc-range shard step cannot run a disjunctive query");
-  try {
-    HIP_OK(hipSetDevice(h->device));
-    HIP_OK(hipMemcpyAsync(b->d_xrecv, host_recv, sizeof(Event) * region_events_of(q_per_owner, slot) * world,
-                          hipMemcpyHostToDevice, b->st));
-  } catch (const std::exception& e) {
-    return fail(WSR_E_HIP, e.what());
-  }
-  return step_replay(h, b, rank, world, q_per_owner, slot, b->st);
-}
-
-// Host-exchange owner replays deferred into a later run's lean kernel (the
-// counterpart of the communicator's deferral, wsr_shard_steps): a separate
-// owner replay launch -- thousands of one-wave workgroups -- costs more than
-// its work beside the persistent kernels of the next batches.
-int wsr_shard_step_replay_deferred(wsr_handle* h, wsr_batch* b, int32_t rank, int32_t world, int32_t q_per_owner,
-                                   int64_t slot, const void* host_recv) {
-  if (!h || !b || !host_recv || world < 1 || rank < 0 || rank >= world || q_per_owner <= 0 || slot <= 0 ||
-      !b->x_fused || b->x_world != world || b->x_qpr != q_per_owner || b->x_slot != slot ||
-      static_cast<int64_t>(q_per_owner) * world != b->nq)
-    return fail(WSR_E_INVALID, "call wsr_shard_step_emit with the same world, q_per_owner and slot first");
-  if (b->cls.has_or) return fail(WSR_E_INVALID, "a doc-range shard step cannot run a disjunctive query");
-  if (b->cls.has_wide)   // (the LDS heap: the replay launch of its own)
-    return wsr_shard_step_replay(h, b, rank, world, q_per_owner, slot, host_recv);
-  try {
-    HIP_OK(hipSetDevice(h->device));
-    if (b->hdef) host_replay_flush(b);   // (an earlier one still waiting: first)
-    ensure_xev(b);
-    HIP_OK(hipMemcpyAsync(b->d_xrecv, host_recv, sizeof(Event) * region_events_of(q_per_owner, slot) * world,
-                          hipMemcpyHostToDevice, b->st));
-    HIP_OK(hipEventRecord(b->xev[0], b->st));
-  } catch (const std::exception& e) {
-    return fail(WSR_E_HIP, e.what());
-  }
-  std::lock_guard<std::mutex> g(h->hdef_mu);
-  b->hdef_rank = rank;
-  b->hdef.store(h);
-  h->hdef_q.push_back(b);
-  return WSR_OK;
-}
-
-// The oldest deferred host replay that a run of b can carry (not b's own),
-// off the queue; its OwnerJob in *oj.
-static wsr_batch* take_host_replay(wsr_handle* h, const wsr_batch* b, OwnerJob* oj) {
-  std::lock_guard<std::mutex> g(h->hdef_mu);
-  for (auto it = h->hdef_q.begin(); it != h->hdef_q.end(); ++it) {
-    wsr_batch* pb = *it;
-    if (pb == b) continue;
-    h->hdef_q.erase(it);
-    // counted before hdef is cleared: an x_join that sees it cleared waits
-    // until the taking run has recorded xev[1] (x_enq)
-    pb->x_req.fetch_add(1, std::memory_order_acq_rel);
-    pb->hdef.store(nullptr);
-    const uint64_t region = region_events_of(pb->x_qpr, pb->x_slot);
-    const uint64_t meta_events = (static_cast<uint64_t>(pb->x_qpr) + 1) / 2;
-    const Event* recv = pb->d_xrecv;
-    *oj = OwnerJob{pb->d_q(), reinterpret_cast<const int32_t*>(recv), recv + meta_events, pb->d_hits,
-                   pb->d_nhits, pb->d_ctr, region * (sizeof(Event) / sizeof(int32_t)), region,
-                   pb->hdef_rank * pb->x_qpr, pb->x_qpr, pb->x_world, pb->stride};
-    return pb;
-  }
-  return nullptr;
-}
-
-// A taken (or still queued, via host_replay_flush) replay on pb's own stream.
-static void host_replay_enqueue(wsr_batch* pb, wsr_handle* h) {
-  if (step_replay(h, pb, pb->hdef_rank, pb->x_world, pb->x_qpr, pb->x_slot, pb->st) == WSR_OK &&
-      hipEventRecord(pb->xev[1], pb->st) == hipSuccess)
-    pb->x_pending = true;
-}
-
-static void host_replay_flush(wsr_batch* b) {
-  wsr_handle* h = b->hdef.load();
-  if (!h) return;
-  {
-    std::lock_guard<std::mutex> g(h->hdef_mu);
-    if (!b->hdef.load()) return;   // (taken by a run meanwhile; x_join waits for its enqueue)
-    for (auto it = h->hdef_q.begin(); it != h->hdef_q.end(); ++it)
-      if (*it == b) {
-        h->hdef_q.erase(it);
-        break;
-      }
-    b->hdef.store(nullptr);
-  }
-  host_replay_enqueue(b, h);
-}
-
 int wsr_batch_fetch_range(wsr_handle* h, wsr_batch* b, int32_t q0, int32_t nq, wsr_hit* hits,
                           int32_t* n_hits) {
   if (!h || !b || q0 < 0 || nq < 0 || q0 + nq > b->nq) return fail(WSR_E_INVALID, "bad range");
   try {
     HIP_OK(hipSetDevice(h->device));
     HIP_OK(hipStreamSynchronize(b->st));
-    if (x_join(b)) HIP_OK(hipEventSynchronize(b->xev[1]));   // a shard step's exchange + replay
+    if (b->x.join()) HIP_OK(hipEventSynchronize(b->x.ev[1]));   // a shard step's exchange + replay
     uint32_t ctr[kNumCounters];
     HIP_OK(hipMemcpy(ctr, b->d_ctr, sizeof ctr, hipMemcpyDeviceToHost));
     if (ctr[kCtrError])
@@ -2100,7 +1124,7 @@ int wsr_debug_wg_stats(wsr_handle* h, wsr_batch* b, uint32_t* out, int32_t max_w
                                     static_cast<size_t>(kStatStride) * rows);
   try {
     HIP_OK(hipStreamSynchronize(b->st));
-    if (x_join(b)) HIP_OK(hipEventSynchronize(b->xev[1]));   // a shard step's exchange + replay
+    if (b->x.join()) HIP_OK(hipEventSynchronize(b->x.ev[1]));   // a shard step's exchange + replay
     HIP_OK(hipMemcpy(out, b->d_stats, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
   } catch (const std::exception& e) {
     return fail(WSR_E_HIP, e.what());

@@ -287,4 +287,19 @@ struct HitDev {
 };
 static_assert(sizeof(HitDev) == 16, "HitDev layout");
 
+// The owner side of a doc-range shard exchange: this rank's nq queries of a
+// batch, from q0, replayed over what every shard sent for them (built by
+// owner_job_of, shard_layout.h; read by owner_replay_meta_kernel and, carried
+// in FusedReplay, by a lean kernel's tail: kernels.h).
+struct OwnerJob {
+  const QueryIn* qs;      // the replayed batch's queries; owned ones from q0
+  const int32_t* meta;    // {count, offset} of owned query i from shard g at meta + g * meta_stride + 2 * i
+  const Event* recv;      // shard g's events at recv + g * stride + offset
+  HitDev* hits;
+  int32_t* n_hits;
+  uint32_t* counters;     // the replayed batch's (error flags)
+  uint64_t meta_stride, stride;
+  int32_t q0, nq, n_shards, hit_stride;
+};
+
 }  // namespace wiser

@@ -111,19 +111,8 @@ constexpr float kItemFixedCost = 4.0f;
 // launch is left between the segment kernels and the exchange.
 // A deferred owner replay (wsr_shard_steps): after their own items, the waves
 // of a lean kernel replay owned queries of an earlier step group's exchange --
-// owner_replay_meta_kernel's work without its launch (nq 0: none).  Only
-// batches without wide queries are deferred.
-struct OwnerJob {
-  const QueryIn* qs;      // the replayed batch's queries; owned ones from q0
-  const int32_t* meta;    // {count, offset} of owned query i from shard g at meta + g * meta_stride + 2 * i
-  const Event* recv;      // shard g's events at recv + g * stride + offset
-  HitDev* hits;
-  int32_t* n_hits;
-  uint32_t* counters;     // the replayed batch's (error flags)
-  uint64_t meta_stride, stride;
-  int32_t q0, nq, n_shards, hit_stride;
-};
-
+// owner_replay_meta_kernel's work without its launch (OwnerJob, engine_types.h;
+// nq 0: none).  Only batches without wide queries are deferred.
 struct FusedReplay {
   uint32_t* q_done;
   HitDev* hits;
@@ -184,13 +173,9 @@ hipError_t launch_wide_replay(const QueryIn* q, const QueryPlan* plan, int nq, c
                               hipStream_t st);
 hipError_t launch_decode_probe(const uint8_t* p, uint32_t bits, uint32_t cnt, bool delta,
                                uint32_t seed, uint32_t* out, hipStream_t st);
-// owner side of the fused exchange: meta[(g * nq + i) * 2] = {count, offset}
-// sent by shard g for owned query i, its events at recv + g * slot + offset
-// (meta of shard g at meta + g * meta_stride, its events at recv + g * stride)
-hipError_t launch_owner_replay_meta(const QueryIn* q, int q0, int nq, int n_shards, const int32_t* meta,
-                                    uint64_t meta_stride, uint64_t stride, const Event* recv, HitDev* hits,
-                                    int hit_stride, int32_t* n_hits, uint32_t* counters, bool any_wide,
-                                    hipStream_t st);
+// owner side of the fused exchange, as a launch of its own (any_wide: the
+// LDS-heap instance too, for the job's queries with k > kMaxK)
+hipError_t launch_owner_replay(const OwnerJob& oj, bool any_wide, hipStream_t st);
 // resident 64-thread segment workgroups per CU
 int segment_kernel_occupancy();
 

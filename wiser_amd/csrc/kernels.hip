@@ -3844,16 +3844,15 @@ int segment_kernel_occupancy() {
   return n;
 }
 
-hipError_t launch_owner_replay_meta(const QueryIn* q, int q0, int nq, int n_shards, const int32_t* meta,
-                                    uint64_t meta_stride, uint64_t stride, const Event* recv, HitDev* hits,
-                                    int hit_stride, int32_t* n_hits, uint32_t* counters, bool any_wide,
-                                    hipStream_t st) {
-  if (nq <= 0) return hipSuccess;
-  hipLaunchKernelGGL(owner_replay_meta_kernel<false>, dim3(nq), dim3(64), 0, st, q, q0, nq, n_shards, meta,
-                     meta_stride, stride, recv, hits, hit_stride, n_hits, counters);
+hipError_t launch_owner_replay(const OwnerJob& oj, bool any_wide, hipStream_t st) {
+  if (oj.nq <= 0) return hipSuccess;
+  hipLaunchKernelGGL(owner_replay_meta_kernel<false>, dim3(oj.nq), dim3(64), 0, st, oj.qs, oj.q0, oj.nq,
+                     oj.n_shards, oj.meta, oj.meta_stride, oj.stride, oj.recv, oj.hits, oj.hit_stride, oj.n_hits,
+                     oj.counters);
   if (any_wide)
-    hipLaunchKernelGGL(owner_replay_meta_kernel<true>, dim3(nq), dim3(64), 0, st, q, q0, nq, n_shards, meta,
-                       meta_stride, stride, recv, hits, hit_stride, n_hits, counters);
+    hipLaunchKernelGGL(owner_replay_meta_kernel<true>, dim3(oj.nq), dim3(64), 0, st, oj.qs, oj.q0, oj.nq,
+                       oj.n_shards, oj.meta, oj.meta_stride, oj.stride, oj.recv, oj.hits, oj.hit_stride,
+                       oj.n_hits, oj.counters);
   return hipGetLastError();
 }
 

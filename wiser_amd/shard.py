@@ -50,7 +50,7 @@ def shard_range(n_docs: int, rank: int, world: int) -> Tuple[int, int]:
     return lo, hi
 
 
-# REGION LAYOUT (engine.cc step_emit / step_replay): world regions of
+# REGION LAYOUT (csrc/shard_layout.h, ShardLayout of one batch): world regions of
 # region_events(qpr, slot) 16-byte events each.  Region o of a sender = the
 # int32 pairs {count, offset in the slot} of owner o's queries i = 0..qpr-1 (a
 # query of count -1 overflowed the slot), padded to whole events, then the
@@ -151,7 +151,7 @@ class NativeShardedSearcher:
 
     def fetch_owned(self, b, qpr: int):
         """The owned slice's results.  No flush first: the fetch joins the
-        batch's own deferred owner replay (x_join enqueues it, under the
+        batch's own deferred owner replay (ShardExchange::join enqueues it, under the
         communicator's lock, from whatever thread fetches), and only that one."""
         hits = (_capi.Hit * (qpr * b.stride))()
         nh = (C.c_int32 * qpr)()
