@@ -166,6 +166,10 @@ typedef struct wsr_batch_stats {
   uint64_t max_query_events; /* the largest per-query event count of the batch */
   double lean_ms;            /* lean_kernel alone (segment_ms spans it and the concurrent
                                 general segment_kernel) */
+  uint64_t skippable_blocks; /* of driver_blocks, the conjunctive lean pipeline's blocks that hold
+                                postings in the image's doc range, none of which passed the score
+                                bound: what skipping whole blocks on a per-block impact maximum
+                                could leave out at most */
 } wsr_batch_stats;
 
 /* HBM bytes of an engine's image, per buffer. */

@@ -826,17 +826,20 @@ int wsr_batch_stats_get(wsr_handle* h, wsr_batch* b, wsr_batch_stats* out) {
     const int rows = b->cls.seg_grid + kLeanWaves * (b->cls.lean_wgs + (b->cls.has_phrase ? b->cls.lean_wgs_ph : 0));
     std::vector<uint32_t> ws(static_cast<size_t>(kStatStride) * rows);
     HIP_OK(hipMemcpy(ws.data(), b->d_stats, ws.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    uint64_t sv = 0, db = 0, ob = 0;
+    uint64_t sv = 0, db = 0, ob = 0, sk = 0;
     for (int i = 0; i < rows; ++i) {
       // (rows of a kernel the last run did not launch hold an earlier run's values)
       const bool conj_row = i >= b->cls.seg_grid && i < b->cls.seg_grid + kLeanWaves * b->cls.lean_wgs;
       if (i < b->cls.seg_grid ? !b->launched.gen : (conj_row && !b->launched.conj)) continue;
-      sv += ws[kStatStride * i]; db += ws[kStatStride * i + 1]; ob += ws[kStatStride * i + 2];
+      // (the third word: a general workgroup's other-list blocks, a lean wave's skippable blocks)
+      sv += ws[kStatStride * i]; db += ws[kStatStride * i + 1];
+      (i < b->cls.seg_grid ? ob : sk) += ws[kStatStride * i + 2];
     }
     out->work_items = ctr[kCtrItems];
     out->survivors = sv;
     out->driver_blocks = db;
     out->other_blocks = ob;
+    out->skippable_blocks = sk;
     out->algo_bytes = b->cls.algo_static + sv;
     {
       const uint32_t items = ctr[kCtrItems];

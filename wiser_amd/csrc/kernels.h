@@ -74,6 +74,7 @@ constexpr uint32_t kPlanPhrase = 1u << 17;
 static_assert(kMaxQueryTerms <= static_cast<int>(kPlanSlotMask) + 1, "driver slot field");
 // per-workgroup statistics written by the segment kernels (no atomics):
 // stats[wg * kStatStride + {0 survivors, 1 driver blocks, 2 other blocks}]
+// (a lean wave's row: 2 = of its driver blocks, those with postings in range whose D stage kept none, lean_segment)
 constexpr int kStatStride = 4;
 enum { kErrLimit = 1, kErrCapacity = 2, kErrExchange = 4, kErrClass = 8 };
 constexpr int kMaxOwners = 1024;   // doc-range shards (ranks) of one exchange

@@ -1911,7 +1911,8 @@ __device__ __forceinline__ void lean_segment(const IndexArgs& ix, LeanLdsT<kPh>&
                                              uint64_t* my_pub,
                                              Event* ev_out, uint32_t& ev_n, uint32_t& evb,
                                              double& pt, uint32_t& pt_n,
-                                             double& last_pub, uint32_t& n_surv, uint32_t& n_dblk) {
+                                             double& last_pub, uint32_t& n_surv, uint32_t& n_dblk,
+                                             uint32_t& n_empty) {
   const uint32_t l = threadIdx.x & 63;
   const uint64_t lt = lanemask_lt();
   const uint32_t d = kTwo ? (Q.slots & 1u) : (Q.slots & 0xFFFFu);
@@ -2390,6 +2391,11 @@ __device__ __forceinline__ void lean_segment(const IndexArgs& ix, LeanLdsT<kPh>&
       }
       Y.da0 = p0 ? a0 : ~0u; Y.da1 = p1 ? a1 : ~0u;
       if (live) ++n_dblk;
+      // (blocks with postings in the image's doc range none of which passed
+      // the score bound: what a per-block impact maximum could skip at most,
+      // DESIGN.md 10.2; a block with no posting in range is not counted, and
+      // a wide item's threshold lets every posting pass)
+      if (kImp && live && __ballot(ok0 | ok1) != 0 && __ballot(p0 | p1) == 0) ++n_empty;
       // past the smallest last doc of the other lists nothing later can match
       const uint64_t past = __ballot((ok0 & (a0 > min_last)) | (ok1 & (a1 > min_last)));
       if (live & (past != 0)) bend = j + 1;
@@ -3266,7 +3272,7 @@ __global__ __launch_bounds__(64 * kLeanWaves, kPh ? kLeanWgsPhrase : kLeanWgs) v
                                                       __HIP_MEMORY_SCOPE_AGENT))
                               : n_conj;
   uint32_t* heads = &counters[kPh ? kCtrPHead0 : kCtrHead0];
-  uint32_t n_surv = 0, n_dblk = 0;
+  uint32_t n_surv = 0, n_dblk = 0, n_empty = 0;
   uint32_t shard = wid % kQueueShards, tried = 0;
   uint32_t item = lo + wid;
   for (;;) {
@@ -3319,10 +3325,10 @@ __global__ __launch_bounds__(64 * kLeanWaves, kPh ? kLeanWgsPhrase : kLeanWgs) v
                             ev_n, evb, pt, pt_n, last_pub, n_surv, n_dblk);
       else if (uni(static_cast<uint32_t>(Q.o_bm >> kProbeShiftBit)))   // O1 has offset buckets
         lean_segment<kPh, kTwo, true, kPh ? 0 : kLeanDeep>(ix, S, norm, Q, ql, phrase, b0, b1, dtail, tdoc0, tdoc1, ttf0, ttf1,
-                                      floor0, prev_pub, r, my_pub, ev_out, ev_n, evb, pt, pt_n, last_pub, n_surv, n_dblk);
+                                      floor0, prev_pub, r, my_pub, ev_out, ev_n, evb, pt, pt_n, last_pub, n_surv, n_dblk, n_empty);
       else
         lean_segment<kPh, kTwo, false, kPh ? 0 : kLeanDeep>(ix, S, norm, Q, ql, phrase, b0, b1, dtail, tdoc0, tdoc1, ttf0, ttf1,
-                                       floor0, prev_pub, r, my_pub, ev_out, ev_n, evb, pt, pt_n, last_pub, n_surv, n_dblk);
+                                       floor0, prev_pub, r, my_pub, ev_out, ev_n, evb, pt, pt_n, last_pub, n_surv, n_dblk, n_empty);
       }
     }
     // The item's end from the events still in LDS where it can (finish_item
@@ -3378,7 +3384,7 @@ __global__ __launch_bounds__(64 * kLeanWaves, kPh ? kLeanWgsPhrase : kLeanWgs) v
   if (l == 0) {
     stats[wid * kStatStride + 0] = n_surv;
     stats[wid * kStatStride + 1] = n_dblk;
-    stats[wid * kStatStride + 2] = 0;
+    stats[wid * kStatStride + 2] = n_empty;
   }
 }
 
