@@ -183,6 +183,8 @@ typedef struct wsr_image_info {
   uint64_t pos_bytes;     /* position boxes (positions = 1) */
   uint32_t n_lists, dense_lists;
   uint64_t impact_bytes;  /* per-posting impact bytes (a part of dir_bytes) */
+  uint64_t doc16_bytes;   /* 16-bit doc ids of the lists whose pack blocks each span at most 65,535
+                             docs (a part of dir_bytes; 0 with WSR_DOC16=0 at load) */
 } wsr_image_info;
 
 const char* wsr_last_error(void);
@@ -483,6 +485,25 @@ int wsr_debug_fail_runs(int32_t n);
 int wsr_debug_dense_lookup(const char* dir, uint32_t doc_lo, uint32_t doc_hi, uint32_t dense_div,
                            const char* term, const uint32_t* docs, int32_t n, int32_t* tf_out,
                            int32_t* is_dense);
+
+/* Host-only view of the 16-bit doc ids (wsr_image_info::doc16_bytes; no GPU):
+ * builds the image of [doc_lo, doc_hi) (doc_hi 0 = all) with wsr_open's
+ * load-time knobs, WSR_DOC16 among them.  *n_blocks = blocks of the term's list
+ * in that image; for its first min(*n_blocks, max_blocks) blocks b, prev[b] =
+ * the block's delta seed as the image holds it; *eligible = 1 when the list has
+ * a run in the array, and then out[128 * b .. 128 * b + 128) receives block b's
+ * slots: doc id - prev[b] per posting, 0 past the block's postings and in a
+ * VInts tail block.  *eligible = 0 ("not eligible") leaves out untouched.
+ * *probe = the list's probe structure in that image: -1 none, 0 a rank bitmap,
+ * else the shift of its offset buckets. */
+int wsr_debug_doc16(const char* dir, uint32_t doc_lo, uint32_t doc_hi, const char* term, int32_t max_blocks,
+                    uint16_t* out, uint32_t* prev, int32_t* n_blocks, int32_t* eligible, int32_t* probe);
+/* Host only, no image: per term its list's blocks in the whole index, of them
+ * the full pack blocks, and of those the ones whose last - prev fits 16 bits
+ * (all 0 for a term not in the index); eligible[i] = 1 when the loader's own
+ * rule gives the list a run in the array of the whole index's image. */
+int wsr_doc16_survey(const char* dir, const char* const* terms, int32_t n, uint32_t* n_blocks,
+                     uint32_t* pack_blocks, uint32_t* ok_blocks, int32_t* eligible);
 
 /* ---- index building (host only; no GPU needed) ----------------------- */
 typedef struct wsr_build_stats {

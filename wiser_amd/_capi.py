@@ -69,7 +69,7 @@ class ImageInfo(C.Structure):
     _fields_ = [("total_bytes", C.c_uint64), ("blob_bytes", C.c_uint64), ("dense_bytes", C.c_uint64),
                 ("tf8_bytes", C.c_uint64), ("plen_bytes", C.c_uint64), ("dir_bytes", C.c_uint64),
                 ("pos_bytes", C.c_uint64), ("n_lists", C.c_uint32), ("dense_lists", C.c_uint32),
-                ("impact_bytes", C.c_uint64)]
+                ("impact_bytes", C.c_uint64), ("doc16_bytes", C.c_uint64)]
 
 
 class ServeStats(C.Structure):
@@ -165,6 +165,11 @@ _sigs = {
     "wsr_debug_dense_lookup": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p,
                                          C.POINTER(C.c_uint32), C.c_int32, C.POINTER(C.c_int32),
                                          C.POINTER(C.c_int32)]),
+    "wsr_debug_doc16": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_int32,
+                                  C.POINTER(C.c_uint16), C.POINTER(C.c_uint32), C.POINTER(C.c_int32),
+                                  C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "wsr_doc16_survey": (C.c_int, [C.c_char_p, C.POINTER(C.c_char_p), C.c_int32, C.POINTER(C.c_uint32),
+                                   C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]),
     "wsr_build_from_linedoc": (C.c_int, [C.c_char_p, C.c_int64, C.c_char_p, C.c_char_p,
                                          C.POINTER(BuildStats)]),
     "wsr_build_from_linedoc_bloom": (C.c_int, [C.c_char_p, C.c_int64, C.c_char_p, C.c_char_p,

@@ -66,6 +66,10 @@ wsr_image_info image_info_of(const HostImage& img, size_t n_c4) {
                 dev_bytes(img.blk_meta) + dev_bytes(img.bmax) + std::max<uint64_t>(n_c4, 1);
   o.impact_bytes = dev_bytes(img.impact);   // (a part of dir_bytes)
   o.dir_bytes += o.impact_bytes;
+  if (!img.doc16.empty()) {   // (a part of dir_bytes, as are the lists' runs in it)
+    o.doc16_bytes = dev_bytes(img.doc16);
+    o.dir_bytes += o.doc16_bytes + dev_bytes(img.d16_blk);
+  }
   o.dense_lists = img.dense_lists;
   o.n_lists = static_cast<uint32_t>(img.lists.size());
   o.total_bytes = o.blob_bytes + o.dense_bytes + o.tf8_bytes + o.plen_bytes + o.dir_bytes + o.pos_bytes;
@@ -75,6 +79,8 @@ wsr_image_info image_info_of(const HostImage& img, size_t n_c4) {
 // the load-time knobs of wsr_open (environment)
 uint32_t dense_div_knob() { return static_cast<uint32_t>(env_number("WSR_DENSE_DIV", 8192)); }
 uint64_t dense_budget_knob() { return static_cast<uint64_t>(env_number("WSR_DENSE_BUDGET_GB", 48) * 1e9); }
+// WSR_DOC16=0: no 16-bit doc ids, every driver's doc ids are unpacked (HostImage::doc16)
+bool doc16_knob() { return env_number("WSR_DOC16", 1) != 0; }
 }  // namespace
 
 extern "C" {
@@ -99,7 +105,8 @@ int wsr_image_size(const char* dir, uint32_t doc_lo, uint32_t doc_hi, int32_t po
     idx.open(dir);
     const int t = threads > 0 ? threads : static_cast<int>(std::thread::hardware_concurrency());
     const HostImage img = build_image(idx, doc_lo, doc_hi ? doc_hi : 0xFFFFFFFFu, std::min(t, 32), dense_div_knob(),
-                                      positions != 0, dense_budget_knob(), positions && bloom_factor > 0);
+                                      positions != 0, dense_budget_knob(), positions && bloom_factor > 0, 0,
+                                      doc16_knob());
     *out = image_info_of(img, idx.char4_lengths().size());
   } catch (const std::exception& e) {
     return fail(WSR_E_IO, e.what());
@@ -158,7 +165,7 @@ int wsr_open(const char* dir, const wsr_open_opts* opts, wsr_handle** out) {
     size_t hbm_free = 0, hbm_total = 0;
     HIP_OK(hipMemGetInfo(&hbm_free, &hbm_total));
     HostImage img = build_image(h->idx, lo, hi, std::min(threads, 32), dense_div, h->positions, dense_budget,
-                                bloom_factor > 0, hbm_free);
+                                bloom_factor > 0, hbm_free, doc16_knob());
     if (img.has_blooms) {   // (counted with the position boxes)
       h->info.pos_bytes += dev_upload(h->d_blm, img.blm);
       h->info.pos_bytes += dev_upload(h->d_blm_hash, img.blm_hash);
@@ -204,6 +211,13 @@ int wsr_open(const char* dir, const wsr_open_opts* opts, wsr_handle** out) {
     h->info.impact_bytes = dev_upload(h->d_impact, img.impact);
     h->info.dir_bytes += h->info.impact_bytes;
     h->args.impact = h->d_impact.get();
+    if (!img.doc16.empty()) {   // (WSR_DOC16=0, or no eligible list: both stay null, every list ineligible)
+      h->info.doc16_bytes = dev_upload(h->d_doc16, img.doc16);
+      h->info.dir_bytes += h->info.doc16_bytes + dev_upload(h->d_d16_blk, img.d16_blk);
+      h->args.doc16 = h->d_doc16.get();
+      h->args.d16_blk = h->d_d16_blk.get();
+      big_vector<uint16_t>().swap(img.doc16);
+    }
     {   // (rounded down: the other terms' bound falls as the norm grows)
       float nm = static_cast<float>(img.norm_min);
       if (static_cast<double>(nm) > img.norm_min) nm = std::nextafter(nm, 0.0f);
@@ -1160,6 +1174,53 @@ int wsr_debug_dense_lookup(const char* dir, uint32_t doc_lo, uint32_t doc_hi, ui
     if (is_dense) *is_dense = dense ? 1 : 0;
     for (int32_t i = 0; i < n; ++i)
       tf_out[i] = dense ? static_cast<int32_t>(dense_lookup_host(img, img.lists[id], docs[i])) : -1;
+  } catch (const std::exception& e) {
+    return fail(WSR_E_IO, e.what());
+  }
+  return WSR_OK;
+}
+
+int wsr_debug_doc16(const char* dir, uint32_t doc_lo, uint32_t doc_hi, const char* term, int32_t max_blocks,
+                    uint16_t* out, uint32_t* prev, int32_t* n_blocks, int32_t* eligible, int32_t* probe) {
+  if (!dir || !term || !n_blocks || !eligible || !probe || max_blocks < 0 || (max_blocks > 0 && (!out || !prev)))
+    return fail(WSR_E_INVALID, "bad argument");
+  try {
+    VacuumIndex idx;
+    idx.open(dir);
+    const HostImage img = build_image(idx, doc_lo, doc_hi ? doc_hi : 0xFFFFFFFFu, 4, dense_div_knob(), false,
+                                      dense_budget_knob(), false, 0, doc16_knob());
+    const int32_t id = idx.find(term);
+    if (id < 0) return fail(WSR_E_INVALID, "no such term");
+    const ListDev& L = img.lists[id];
+    *n_blocks = static_cast<int32_t>(L.nblk);
+    *probe = L.bm == kNoDense ? -1 : static_cast<int32_t>(probe_shift(L.bm));
+    *eligible = !img.d16_blk.empty() && img.d16_blk[id] != kNoDoc16;
+    for (uint32_t b = 0; b < L.nblk && b < static_cast<uint32_t>(max_blocks); ++b) {
+      prev[b] = img.blocks[L.blk0 + b].prev;
+      if (*eligible)
+        std::memcpy(out + 128ull * b, &img.doc16[(static_cast<uint64_t>(img.d16_blk[id]) + b) * 128],
+                    128 * sizeof(uint16_t));
+    }
+  } catch (const std::exception& e) {
+    return fail(WSR_E_IO, e.what());
+  }
+  return WSR_OK;
+}
+
+int wsr_doc16_survey(const char* dir, const char* const* terms, int32_t n, uint32_t* n_blocks,
+                     uint32_t* pack_blocks, uint32_t* ok_blocks, int32_t* eligible) {
+  if (!dir || (n > 0 && (!terms || !n_blocks || !pack_blocks || !ok_blocks || !eligible)))
+    return fail(WSR_E_INVALID, "null argument");
+  try {
+    VacuumIndex idx;
+    idx.open(dir);
+    for (int32_t i = 0; i < n; ++i) {
+      const int32_t id = terms[i] ? idx.find(terms[i]) : -1;
+      n_blocks[i] = pack_blocks[i] = ok_blocks[i] = 0;
+      bool ok = false;
+      if (id >= 0) doc16_survey(idx, id, &n_blocks[i], &pack_blocks[i], &ok_blocks[i], &ok);
+      eligible[i] = ok ? 1 : 0;
+    }
   } catch (const std::exception& e) {
     return fail(WSR_E_IO, e.what());
   }

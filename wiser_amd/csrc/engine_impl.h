@@ -59,6 +59,8 @@ struct wsr_handle {
   gpu::DevBuf<uint32_t> d_dense_rk;   // the bitmap entries' rank records
   gpu::DevBuf<uint32_t> d_bkt;        // offset buckets (entries and offset bytes)
   gpu::DevBuf<uint8_t> d_tf8, d_plen, d_impact;
+  gpu::DevBuf<uint16_t> d_doc16;      // 16-bit doc ids of the eligible lists
+  gpu::DevBuf<uint32_t> d_d16_blk;    //   and each list's run in them
   gpu::DevBuf<float> d_bmax;
   gpu::DevBuf<uint32_t> d_tails;
   gpu::DevBuf<uint8_t> d_pos_blob;    // positions (opened with wsr_open_opts::positions)

@@ -55,6 +55,20 @@ inline uint8_t impact_byte(uint32_t tf, double nrm) {
   return static_cast<uint8_t>(q);
 }
 
+// 16-bit doc ids of a driver (HostImage::doc16): slot p of block b holds
+// doc(b, p) - BlockDev::prev(b), so the lean pipeline reads a posting's doc id
+// as one add instead of unpacking and prefix-summing the block's deltas.  A
+// block is eligible when it is a full pack block whose last - prev fits 16
+// bits; a list when every pack block of it in the image is (at least one; its
+// VInts tail block is not counted: the kernels read the decoded tail).  Only
+// eligible lists have a run in the array, one entry per block of the list in
+// the image, the tail block's zero (HostImage::d16_blk).
+constexpr uint32_t kDoc16Span = 65535;
+constexpr uint32_t kNoDoc16 = ~0u;
+inline bool doc16_block_ok(bool full_pack, uint32_t prev, uint32_t last) {
+  return full_pack && last >= prev && last - prev <= kDoc16Span;
+}
+
 // A list's probe structure (ListDev::bm, QueryDesc::o_bm): bits 0-55 its
 // first entry, bits 56-63 the bucket shift c (0: a rank bitmap of DenseEnt).
 //
@@ -223,7 +237,9 @@ struct QueryDesc {
   uint64_t o_bm;        // O1 (the other list with the fewest blocks): first bitmap entry
   uint64_t o_tf8;       //   offset of its 1-byte tfs
   uint64_t ev_base;     // = QueryPlan::ev_base
-  uint64_t rsv0, rsv1;
+  uint32_t a_d16;       // driver: first block of its run in doc16 (kNoDoc16: decode its packs)
+  uint32_t rsv0;
+  uint64_t rsv1;
   double a_idf, o_idf;
   uint32_t a_blk0, a_nblk, a_tail_cnt;
   uint32_t min_last;    // smallest last doc id over the other lists

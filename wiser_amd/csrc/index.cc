@@ -344,13 +344,30 @@ void for_each_list(int32_t L, int threads, F&& fn) {
 }
 }  // namespace
 
+// The list rule of doc16 (engine_types.h), stated once for the loader and for
+// doc16_survey: every block of rows [r0, r1) but a VInts tail (the last row,
+// vtail) is a full pack block whose span fits 16 bits, and there is one.
+// last(r), cnt(r): the row's last doc id and its postings.
+template <class Last, class Cnt>
+static bool doc16_list_ok(const uint8_t* file, const SkipRow* rows, uint64_t r0, uint64_t r1, bool vtail, Last last,
+                          Cnt cnt) {
+  const uint64_t np = r1 - r0 - (vtail ? 1 : 0);
+  bool ok = r1 > r0 && np > 0;
+  for (uint64_t r = r0; r < r0 + np && ok; ++r)
+    ok = doc16_block_ok(file[rows[r].doc_off] == kPackMagic && cnt(r) == kPackSize, rows[r].prev_doc, last(r));
+  return ok;
+}
+// doc16 is indexed by 32-bit dword arithmetic in the kernels (block * 64 + lane): an array of
+// this many blocks or more (16 GiB) is not built, and every list stays ineligible
+constexpr uint64_t kDoc16MaxBlocks = 1ull << 26;
+
 // Three passes over the lists, none of which allocates per list: (1) size the
 // list's part of every image array, (2) prefix sums in list-id order, (3) fill
 // the arrays in place.  (Millions of one-block lists -- the en-Wikipedia shape
 // -- made per-list vectors and their serial concatenation the load's cost.)
 HostImage build_image(const VacuumIndex& idx, uint32_t doc_lo, uint32_t doc_hi, int threads,
                       uint32_t dense_div, bool positions, uint64_t dense_budget, bool blooms,
-                      uint64_t hbm_free) {
+                      uint64_t hbm_free, bool doc16) {
   const int32_t L = idx.n_lists();
   const uint8_t* file = idx.file();
   const uint8_t* fend = file + idx.file_bytes();
@@ -367,6 +384,7 @@ HostImage build_image(const VacuumIndex& idx, uint32_t doc_lo, uint32_t doc_hi, 
     uint64_t bytes = 0;        // docid span + tf span
     uint8_t dense = 0, vtail = 0;
     uint8_t shift = 0;         // dense: bucket shift (0: a bitmap)
+    uint8_t d16 = 0;           // eligible for doc16 (engine_types.h)
   };
   std::vector<Info> info(L);
   struct Scratch {   // per worker thread, reused from list to list
@@ -431,6 +449,9 @@ HostImage build_image(const VacuumIndex& idx, uint32_t doc_lo, uint32_t doc_hi, 
     in.tail_cnt = (r1 == nrows) ? in.fcnt : kPackSize;
     in.vtail = r1 == nrows && file[s.rows[nrows - 1].doc_off] == kVIntsMagic;
     const uint64_t n_img = (r1 - r0 - 1) * kPackSize + in.tail_cnt;
+    if (doc16)
+      in.d16 = doc16_list_ok(file, s.rows.data(), r0, r1, in.vtail, [&](uint64_t r) { return s.last[r]; },
+                             [&](uint64_t r) { return row_cnt(in, r, nrows); });
     if (dense_div && span && n_img * dense_div >= span) {
       // a doc inside [doc_lo, doc_hi) but past the doc-length records cannot be
       // represented in a bitmap: such a list stays on the block path
@@ -493,7 +514,8 @@ HostImage build_image(const VacuumIndex& idx, uint32_t doc_lo, uint32_t doc_hi, 
       const Info& in = info[id];
       if (in.r1 <= in.r0) continue;
       const uint64_t nbl = in.r1 - in.r0;
-      other += in.bytes + nbl * (sizeof(BlockDev) + 12 + 2 * kPackSize) + (in.vtail ? 8ull * in.tail_cnt : 0);
+      other += in.bytes + nbl * (sizeof(BlockDev) + 12 + (in.d16 ? 4 : 2) * kPackSize) +
+               (in.vtail ? 8ull * in.tail_cnt : 0);
       if (blooms && positions) other += nbl * kPackSize * 32;
     }
     const uint64_t cap = hbm_free / 10 * 9;
@@ -526,7 +548,15 @@ HostImage build_image(const VacuumIndex& idx, uint32_t doc_lo, uint32_t doc_hi, 
   img.lists.resize(L);
   img.list_bytes.resize(L);
   img.has_positions = positions;
-  uint64_t at = 0, nb = 0, ne = 0, ntf8 = 0, ntail = 0, nbk = 0;
+  uint64_t at = 0, nb = 0, ne = 0, ntf8 = 0, ntail = 0, nbk = 0, nd16 = 0;
+  {   // (past the kernels' 32-bit indexing: no array)
+    uint64_t want = 0;
+    for (int32_t id = 0; id < L; ++id)
+      if (info[id].d16) want += info[id].r1 - info[id].r0;
+    if (want >= kDoc16MaxBlocks)
+      for (int32_t id = 0; id < L; ++id) info[id].d16 = 0;
+  }
+  if (doc16) img.d16_blk.assign(L, kNoDoc16);
   for (int32_t id = 0; id < L; ++id) {
     const Info& in = info[id];
     ListDev& ld = img.lists[id];
@@ -544,6 +574,7 @@ HostImage build_image(const VacuumIndex& idx, uint32_t doc_lo, uint32_t doc_hi, 
     ld.tfmax = 0;
     if (!nbl) { img.list_bytes[id] = 0; continue; }
     if (in.vtail) { ld.tail = ntail; ntail += 2ull * in.tail_cnt; }
+    if (in.d16) { img.d16_blk[id] = static_cast<uint32_t>(nd16); nd16 += nbl; }   // (nd16 < kDoc16MaxBlocks)
     if (in.dense) {
       const uint64_t n_img = (nbl - 1) * static_cast<uint64_t>(kPackSize) + in.tail_cnt;
       if (in.shift) {   // offset buckets (nbk: in words, entries are 8-byte aligned)
@@ -572,6 +603,7 @@ HostImage build_image(const VacuumIndex& idx, uint32_t doc_lo, uint32_t doc_hi, 
   img.blk_meta.resize(nb);
   img.plen.resize(nb * kPackSize);
   img.impact.resize(nb * kPackSize);
+  img.doc16.resize(nd16 * kPackSize);
   img.bmax.resize(nb);
   img.tails.resize(ntail);
   img.dense.resize(ne);
@@ -673,6 +705,12 @@ HostImage build_image(const VacuumIndex& idx, uint32_t doc_lo, uint32_t doc_hi, 
         s.code_used[o[i]] = true;
       }
       for (int i = cnt; i < kPackSize; ++i) im[i] = 0;
+      if (in.d16) {   // the block's doc ids from its prev (a VInts tail block: zeros, never read as ids)
+        uint16_t* dd = &img.doc16[(img.d16_blk[id] + (r - r0)) * kPackSize];
+        const int n16 = last_vints ? 0 : cnt;
+        for (int i = 0; i < n16; ++i) dd[i] = static_cast<uint16_t>(docs[i] - s.rows[r].prev_doc);
+        for (int i = n16; i < kPackSize; ++i) dd[i] = 0;
+      }
       float bmf = static_cast<float>(bm);
       if (static_cast<double>(bmf) < bm) bmf = std::nextafter(bmf, std::numeric_limits<float>::infinity());
       img.bmax[j] = bmf;
@@ -936,6 +974,33 @@ int64_t dense_lookup_host(const HostImage& img, const ListDev& L, uint32_t doc) 
   if (!host_decode_block(p, img.blob.data() + img.blob.size(), static_cast<int>(cnt), false, 0, out))
     return -1;
   return out[idx % kPackSize];
+}
+
+void doc16_survey(const VacuumIndex& idx, int32_t id, uint32_t* nblk, uint32_t* pack_blocks, uint32_t* ok_blocks,
+                  bool* list_ok) {
+  const std::vector<SkipRow> rows = idx.rows(id);
+  const uint8_t* file = idx.file();
+  const uint64_t nrows = rows.size();
+  const uint32_t df = idx.df(id);
+  if (nrows == 0 || nrows != (df + kPackSize - 1) / kPackSize)
+    throw std::runtime_error("skip rows do not match df for '" + idx.term(id) + "'");
+  const uint32_t fcnt = static_cast<uint32_t>(df - kPackSize * (nrows - 1));
+  uint32_t tmp[kPackSize];
+  if (!host_decode_block(file + rows[nrows - 1].doc_off, file + idx.file_bytes(), static_cast<int>(fcnt), true,
+                         rows[nrows - 1].prev_doc, tmp))
+    throw std::runtime_error("cannot decode the last block of '" + idx.term(id) + "'");
+  uint32_t np = 0, ok = 0;
+  auto last = [&](uint64_t r) { return r + 1 < nrows ? rows[r + 1].prev_doc : tmp[fcnt - 1]; };
+  auto cnt = [&](uint64_t r) { return r + 1 < nrows ? kPackSize : static_cast<int>(fcnt); };
+  for (uint64_t r = 0; r < nrows; ++r) {
+    const bool full = file[rows[r].doc_off] == kPackMagic && cnt(r) == kPackSize;
+    np += full;
+    ok += doc16_block_ok(full, rows[r].prev_doc, last(r));
+  }
+  *nblk = static_cast<uint32_t>(nrows);
+  *pack_blocks = np;
+  *ok_blocks = ok;
+  *list_ok = doc16_list_ok(file, rows.data(), 0, nrows, file[rows[nrows - 1].doc_off] == kVIntsMagic, last, cnt);
 }
 
 }  // namespace wiser

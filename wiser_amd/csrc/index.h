@@ -141,6 +141,11 @@ struct HostImage {
   big_vector<uint8_t> impact;   // per posting, laid out as plen: impact_byte(tf, cache_[c4]), an
                                 // upper bound of tf / (tf + cache_[c4]) in 1/255 steps, 0 past a
                                 // block's postings (the lean pipeline's pre-probe pruning)
+  big_vector<uint16_t> doc16;   // per posting of the eligible lists (engine_types.h, kDoc16Span), 128
+                                // slots per block as plen: doc id - BlockDev::prev of its block; 0 past
+                                // a block's postings and in a VInts tail block
+  std::vector<uint32_t> d16_blk;   // per list id: the first block of its run in doc16 (its block b of the
+                                   // image at d16_blk + b), kNoDoc16 when not eligible; empty: not built
   double norm_min = 0.0;        // the smallest cache_[c4] over the image's postings
   // positions (build_image(..., positions = true)): see PosDev
   bool has_positions = false;
@@ -177,9 +182,18 @@ bool host_decode_block(const uint8_t* p, const uint8_t* end, int cnt, bool delta
 // bytes of all bitmaps + tf arrays (the longest lists keep theirs).  hbm_free >
 // 0 (the device's free bytes): the budget is also clamped to 90 % of it minus
 // the rest of the image, so that an image never fails to fit for its bitmaps.
+// doc16: build the 16-bit doc ids of the eligible lists (else every list is
+// ineligible and the array stays empty).
 HostImage build_image(const VacuumIndex& idx, uint32_t doc_lo, uint32_t doc_hi, int threads,
                       uint32_t dense_div = 0, bool positions = false, uint64_t dense_budget = 0,
-                      bool blooms = false, uint64_t hbm_free = 0);
+                      bool blooms = false, uint64_t hbm_free = 0, bool doc16 = false);
+
+// The blocks of list id in the whole index, and of them the full pack blocks
+// and the doc16-eligible ones (engine_types.h doc16_block_ok), from its skip
+// rows alone, and whether the list is eligible by the loader's own rule (for
+// the whole index): what scripts/doc16_share.py weighs a query log by.
+void doc16_survey(const VacuumIndex& idx, int32_t id, uint32_t* nblk, uint32_t* pack_blocks, uint32_t* ok_blocks,
+                  bool* list_ok);
 
 // Host restatement of the device's dense probe (bitmap or buckets): tf of doc
 // in list L of the image, -1 when absent or when L has no probe structure.

@@ -33,6 +33,10 @@ struct IndexArgs {
   const uint8_t* plen;      // doc-length code of each posting, 128 per block (HostImage::plen)
   const float* bmax;        // per block: its largest TfNormLossy, f32 rounded up (HostImage::bmax)
   const uint8_t* impact;    // impact byte of each posting, 128 per block as plen (HostImage::impact)
+  const uint16_t* doc16;    // doc id - BlockDev::prev of each posting of the eligible lists, 128 per
+                            // block (HostImage::doc16)
+  const uint32_t* d16_blk;  // per list: the first block of its run in doc16, kNoDoc16 when it has
+                            // none (null: the array was not built)
   float norm_min;           // the smallest doc-length norm of the image's postings, f32 rounded down
                             // (HostImage::norm_min): the lean pipeline bounds the other terms there
   const uint32_t* tails;    // decoded VInts last blocks (ListDev::tail)

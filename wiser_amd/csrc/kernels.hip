@@ -630,6 +630,8 @@ __global__ __launch_bounds__(kPlanThreads) void plan_query_kernel(IndexArgs ix, 
         D.a_blk0 = A.blk0;
         D.a_nblk = A.nblk;
         D.a_tail_cnt = A.tail_cnt;
+        D.a_d16 = ix.d16_blk ? ix.d16_blk[ql[d]] : kNoDoc16;
+        D.rsv0 = 0; D.rsv1 = 0;
         D.o_bm = 0; D.o_tf8 = 0; D.o_idf = 0.0; D.o_list = 0;
         if (o1 != kNoSlot) {
           const ListDev O = ix.lists[ql[o1]];
@@ -1902,7 +1904,11 @@ struct LeanLdsT {
 // D loads its bucket entry, H matches the offset and loads the hit's tf word,
 // C resolves the rare probe past a bucket's fourth posting from its offset
 // bytes.  The same pipeline otherwise.
-template <bool kPh, bool kTwo = false, bool kBk = false, int kDeep = 0>
+// kD16 (conjunctive instances only): the driver has a run in doc16 (the item's
+// QueryDesc::a_d16): W loads one dword per lane, the 16-bit offsets of
+// postings 2l and 2l + 1 from the block's prev, in place of the three pack
+// words, and D forms each doc id with one add: no unpack, no prefix sum.
+template <bool kPh, bool kTwo = false, bool kBk = false, int kDeep = 0, bool kD16 = false>
 __device__ __forceinline__ void lean_segment(const IndexArgs& ix, LeanLdsT<kPh>& S, const double* norm_tab,
                                              const QueryDesc& Q, const int32_t* qlist,
                                              bool phrase, uint32_t b0, uint32_t b1, bool dtail,
@@ -1951,7 +1957,8 @@ __device__ __forceinline__ void lean_segment(const IndexArgs& ix, LeanLdsT<kPh>&
   // and the slot's dependent loads in front of every chunk cost its leg 3 %
   // (DESIGN.md 5.0000).
   constexpr bool kImp = !kPh;
-  uint32_t* qdoc = S.q;             // survivor queue (ring of 256)
+  static_assert(!kD16 || kImp, "16-bit doc ids: the conjunctive instances only");
+  uint32_t* qdoc = S.q;            // survivor queue (ring of 256)
   uint32_t* qc4 = qdoc + 256;       // (!kImp) doc-length code
   uint32_t* qtd = qdoc + 512;       // (!kImp) driver tf
   uint32_t* qto = qdoc + 768;       // tf byte, or 0x80000000 | posting index when escaped
@@ -2165,7 +2172,9 @@ __device__ __forceinline__ void lean_segment(const IndexArgs& ix, LeanLdsT<kPh>&
     // (the block's pack widths and blob offsets are read again from the
     // directory in LDS where they are used, so that no scalar registers hold
     // them across the iteration)
-    uint32_t w0 = 0, w1 = 0, w2 = 0;               // doc-id pack words of the next block
+    uint32_t w0 = 0, w1 = 0, w2 = 0;               // doc-id pack words of the next block (kD16: w0 alone,
+                                                   // its two 16-bit doc offsets; w1 and w2 are never
+                                                   // written or read, so no register holds them)
     uint32_t wi = 0;                               //   its impact bytes (postings 2l, 2l + 1)
     uint32_t wc = 0;                               //   (!kImp) its doc-length codes (2 bytes of a word)
     uint32_t wt0 = 0, wt1 = 0, wt2 = 0;            //   (!kImp) its driver tf pack words
@@ -2198,9 +2207,12 @@ __device__ __forceinline__ void lean_segment(const IndexArgs& ix, LeanLdsT<kPh>&
     const uint32_t bi = b < b1 ? b - b0 : 0u;
     const uint32_t m = uni(S.dmeta[bi]);
     const uint4 e = S.dblk[bi];
-    // (VInts tail: width 0 -> a harmless dummy read)
+    // (VInts tail: width 0 -> a harmless dummy read; kD16: its zero slots)
     uint32_t sh;
-    pair_words(a_blob + uni(e.z) + 2, (m & 0xFF) ? (m & 0xFF) : 1u, l, Y.w0, Y.w1, Y.w2, sh);
+    if constexpr (kD16)
+      Y.w0 = reinterpret_cast<const uint32_t*>(ix.doc16)[(Q.a_d16 + (b < b1 ? b : b0)) * 64u + l];
+    else
+      pair_words(a_blob + uni(e.z) + 2, (m & 0xFF) ? (m & 0xFF) : 1u, l, Y.w0, Y.w1, Y.w2, sh);
     // its impact bytes (postings 2l, 2l+1: one line per block), so that D can
     // bound each posting's score before the probe (!kImp: its doc-length
     // codes, one line per block, and driver tf words)
@@ -2352,12 +2364,18 @@ __device__ __forceinline__ void lean_segment(const IndexArgs& ix, LeanLdsT<kPh>&
       const uint32_t prev = uni(be.x);
       const uint32_t wbits = (m & 0xFF) ? (m & 0xFF) : 1u;
       const uint32_t cnt = live ? ((j == Q.a_nblk - 1) ? Q.a_tail_cnt : 128u) : 0u;
-      uint32_t x0, x1;
-      pair_values(X.w0, X.w1, X.w2, pair_shift(uni(be.z), wbits), wbits, x0, x1);
-      const uint32_t sm = x0 + x1;
-      const uint32_t inc = wave_incl_scan(sm);
-      uint32_t a0 = prev + (inc - sm) + x0;
-      uint32_t a1 = a0 + x1;
+      uint32_t a0, a1;
+      if constexpr (kD16) {
+        a0 = prev + (X.w0 & 0xFFFFu);
+        a1 = prev + (X.w0 >> 16);
+      } else {
+        uint32_t x0, x1;
+        pair_values(X.w0, X.w1, X.w2, pair_shift(uni(be.z), wbits), wbits, x0, x1);
+        const uint32_t sm = x0 + x1;
+        const uint32_t inc = wave_incl_scan(sm);
+        a0 = prev + (inc - sm) + x0;
+        a1 = a0 + x1;
+      }
       const bool tl = live && dtail && j == b1 - 1;
       if (tl) { a0 = tdoc0; a1 = tdoc1; }
       const bool ok0 = (2 * l < cnt) & (a0 - lo < hi_rel);
@@ -3255,6 +3273,12 @@ __global__ __launch_bounds__(64 * kLeanWaves, kPh ? kLeanWgsPhrase : kLeanWgs) v
     uint64_t* __restrict__ pub, const QueryDesc* __restrict__ desc) {
   __shared__ LeanLdsT<kPh> SW[kLeanWaves];
   __shared__ double norm[256];
+  // An item whose driver has 16-bit doc ids runs lean_segment's kD16 copy,
+  // chosen as the bucket copy is, by a uniform branch on its record.  The
+  // two-term instance only: with four copies of the pipeline the general
+  // instance would be 97 KB of code (56 KB with two), past the 64 KB
+  // instruction cache.
+  constexpr bool kD16Item = kTwo && !kPh;
   const uint32_t l = threadIdx.x & 63;
   // (wave-uniform; said so, so that the item indices, segment bounds and the
   // pipeline's loop counter derived from it are scalar, not per-lane values)
@@ -3323,6 +3347,12 @@ __global__ __launch_bounds__(64 * kLeanWaves, kPh ? kLeanWgsPhrase : kLeanWgs) v
         single_segment<kPh>(ix, S, norm, Q, b0, b1, dtail, tdoc0, tdoc1, ttf0, ttf1, floor0, prev_pub, r, my_pub,
                             ev_out,
                             ev_n, evb, pt, pt_n, last_pub, n_surv, n_dblk);
+      else if (kD16Item && uni(Q.a_d16) != kNoDoc16 && uni(static_cast<uint32_t>(Q.o_bm >> kProbeShiftBit)))
+        lean_segment<kPh, kTwo, true, kPh ? 0 : kLeanDeep, kD16Item>(ix, S, norm, Q, ql, phrase, b0, b1, dtail, tdoc0, tdoc1, ttf0, ttf1,
+                                      floor0, prev_pub, r, my_pub, ev_out, ev_n, evb, pt, pt_n, last_pub, n_surv, n_dblk, n_empty);
+      else if (kD16Item && uni(Q.a_d16) != kNoDoc16)   // the driver has 16-bit doc ids
+        lean_segment<kPh, kTwo, false, kPh ? 0 : kLeanDeep, kD16Item>(ix, S, norm, Q, ql, phrase, b0, b1, dtail, tdoc0, tdoc1, ttf0, ttf1,
+                                       floor0, prev_pub, r, my_pub, ev_out, ev_n, evb, pt, pt_n, last_pub, n_surv, n_dblk, n_empty);
       else if (uni(static_cast<uint32_t>(Q.o_bm >> kProbeShiftBit)))   // O1 has offset buckets
         lean_segment<kPh, kTwo, true, kPh ? 0 : kLeanDeep>(ix, S, norm, Q, ql, phrase, b0, b1, dtail, tdoc0, tdoc1, ttf0, ttf1,
                                       floor0, prev_pub, r, my_pub, ev_out, ev_n, evb, pt, pt_n, last_pub, n_surv, n_dblk, n_empty);
