@@ -8,6 +8,7 @@ LIB     := wiser_amd/_lib/libwiser_hip.so
 ORACLE  := oracle/_build/liboracle.so
 SRCS    := wiser_amd/csrc/writer.cc wiser_amd/csrc/index.cc wiser_amd/csrc/engine.cc \
            wiser_amd/csrc/shard_exchange.cc wiser_amd/csrc/batch_plan.cc wiser_amd/csrc/server.cc \
+           wiser_amd/csrc/score_plan.cc wiser_amd/csrc/score_docs.cc \
            wiser_amd/csrc/docstore.cc \
            wiser_amd/csrc/snippet.cc wiser_amd/csrc/kernels.hip
 HDRS    := $(wildcard wiser_amd/csrc/*.h) include/wiser_hip.h
@@ -25,12 +26,16 @@ DICT    := wiser_amd/_lib/dict_check
 DEVMEM  := wiser_amd/_lib/dev_mem_check
 BPLAN   := wiser_amd/_lib/batch_plan_check
 SLAYOUT := wiser_amd/_lib/shard_layout_check
+SPLAN   := wiser_amd/_lib/score_plan_check
+SCLI    := wiser_amd/_lib/score_cli
 
-# (the buffer owner's, the upload plan's and the shard layout's checks are tests of those files
+# (the buffer owner's, the two plans' and the shard layout's checks are tests of those files
 # alone: a tree whose tests/ does not hold their sources still builds everything else)
 all: $(LIB) $(ORACLE) $(CLI) $(CALIB) $(DICT) $(if $(wildcard tests/cpp/dev_mem_check.cc),$(DEVMEM)) \
      $(if $(wildcard tests/cpp/batch_plan_check.cc),$(BPLAN)) \
-     $(if $(wildcard tests/cpp/shard_layout_check.cc),$(SLAYOUT))
+     $(if $(wildcard tests/cpp/shard_layout_check.cc),$(SLAYOUT)) \
+     $(if $(wildcard tests/cpp/score_plan_check.cc),$(SPLAN)) \
+     $(if $(wildcard tests/cpp/score_cli.cc),$(SCLI))
 
 # CPU check of the term dictionary (tests/test_dictionary.py)
 $(DICT): tests/cpp/dict_check.cc wiser_amd/csrc/index.h $(LIB)
@@ -53,6 +58,12 @@ $(SLAYOUT): tests/cpp/shard_layout_check.cc wiser_amd/csrc/shard_layout.h wiser_
 	@mkdir -p wiser_amd/_lib
 	$(CXX) -O2 -std=c++17 -Wall -o $@ tests/cpp/shard_layout_check.cc
 
+# CPU check of the wsr_score_docs plan on a hand-made image (tests/test_score_plan.py): no HIP, no engine
+$(SPLAN): tests/cpp/score_plan_check.cc wiser_amd/csrc/score_plan.cc wiser_amd/csrc/score_plan.h \
+          wiser_amd/csrc/batch_plan.h wiser_amd/csrc/engine_types.h include/wiser_hip.h
+	@mkdir -p wiser_amd/_lib
+	$(CXX) -O2 -std=c++17 -Wall -o $@ tests/cpp/score_plan_check.cc wiser_amd/csrc/score_plan.cc
+
 # counter calibration (profiles only): known-byte reads for rocprofv3 --pmc
 $(CALIB): scripts/calib_ea.hip
 	@mkdir -p wiser_amd/_lib
@@ -60,6 +71,10 @@ $(CALIB): scripts/calib_ea.hip
 
 $(CLI): tests/cpp/engine_cli.cc include/wiser_hip_engine.hpp include/wiser_hip.h $(LIB)
 	$(CXX) -O2 -std=c++17 -Iinclude -o $@ tests/cpp/engine_cli.cc -Lwiser_amd/_lib -lwiser_hip -Wl,-rpath,'$$ORIGIN'
+
+# C++ host of the (query, doc) scoring mirror (tests/test_gpu_score_docs.py)
+$(SCLI): tests/cpp/score_cli.cc include/wiser_hip_engine.hpp include/wiser_hip.h $(LIB)
+	$(CXX) -O2 -std=c++17 -Iinclude -o $@ tests/cpp/score_cli.cc -Lwiser_amd/_lib -lwiser_hip -Wl,-rpath,'$$ORIGIN'
 
 $(OBJDIR)/%.o: wiser_amd/csrc/% $(HDRS)
 	@mkdir -p $(OBJDIR)

@@ -29,8 +29,8 @@
  *
  * Threading: a handle may be used from several threads (the reference's
  * engine is shared read-only by its gRPC threads, grpc_server_impl.h:260-263):
- * its image is read-only after wsr_open, wsr_search_batch / wsr_search_text
- * may be called concurrently, and threads that each own a wsr_batch drive
+ * its image is read-only after wsr_open, wsr_search_batch / wsr_search_text /
+ * wsr_score_docs may be called concurrently, and threads that each own a wsr_batch drive
  * them concurrently (a batch itself is used by one thread at a time).
  */
 #ifndef WISER_HIP_H
@@ -225,6 +225,34 @@ int wsr_check_query(wsr_handle* h, const wsr_query* q);
  * every query's k); n_hits[q] = entries written for query q. */
 int wsr_search_batch(wsr_handle* h, const wsr_query* q, int32_t nq, int32_t hit_stride,
                      wsr_hit* hits, int32_t* n_hits);
+
+/* What the engine's BM25 gives each of the caller's (query, doc) pairs (beyond
+ * the reference: re-ranking a candidate set of another retriever, explaining a
+ * hit, asking a doc-range shard about docs that only it holds).  Query i's
+ * candidates are docs[doc_off[i] .. doc_off[i + 1]) (doc_off: nq + 1 entries,
+ * ascending from doc_off[0] = 0), in any order, duplicates allowed; out[j]
+ * answers docs[j].  mask: bit t is set iff term t has a list (list_ids[t] >= 0)
+ * and that list holds the doc.  score: from 0.0, for each set bit in query
+ * order, score = score + the BM25 term (a term given twice counts twice) -- a
+ * doc with a full mask scores its conjunctive score bit for bit, any doc its
+ * WSR_QUERY_OR score, and mask 0 gives 0.0.  k is ignored; WSR_QUERY_OR is
+ * accepted and changes nothing.  n_terms > WSR_MAX_TERMS is WSR_E_LIMIT;
+ * WSR_QUERY_PHRASE on two or more terms (positions are not checked here),
+ * unknown flags, a list id below -1 or past the index, a doc id outside
+ * [0, n_docs) of the whole index and a doc_off that does not ascend from 0 are
+ * WSR_E_INVALID: all checked before anything is enqueued.  On a doc-range shard
+ * engine a doc outside the image's range answers {0.0, 0}: each doc lives in
+ * one shard, so a caller that asks every shard takes the one non-zero answer.
+ * Synchronous; may be called concurrently on one handle; nq = 0 and a query
+ * without candidates are fine; at most 2^31 - 1 candidates per call
+ * (WSR_E_LIMIT). */
+typedef struct wsr_doc_score {
+  double score;
+  uint32_t mask;
+  int32_t pad;
+} wsr_doc_score;
+int wsr_score_docs(wsr_handle* h, const wsr_query* q, int32_t nq, const int64_t* doc_off,
+                   const int32_t* docs, wsr_doc_score* out);
 
 /* Queries as text, the reference's query-log format (QueryProducerByLog,
  * query_pool.h:319-378): one query per line, terms separated by spaces, a

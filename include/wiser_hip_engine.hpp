@@ -47,6 +47,11 @@ struct SearchResult {  // types.h:297-346
   const SearchResultEntry& operator[](int i) const { return entries[i]; }
 };
 
+struct DocScore {  // what a query gives one doc (ScoreDocs; beyond the reference)
+  double score = 0;
+  uint32_t mask = 0;   // bit t: term t is in the index and its list holds the doc
+};
+
 inline void check(int rc) {
   if (rc != WSR_OK) throw std::runtime_error(std::string("wiser_hip: ") + wsr_last_error());
 }
@@ -95,6 +100,42 @@ class VacuumHipEngine {
     }
     s.resize(n);
     return s;
+  }
+
+  // wsr_score_docs: per query, what it gives each of its doc ids, in the
+  // caller's order.  mask bit t: term t is in the index and its list holds the
+  // doc; score: the sum of those terms' BM25 in query order from 0.0 (a full
+  // mask: the conjunctive score; any mask: the match_any score).  n_results is
+  // ignored; the engine checks the term limit (WSR_MAX_TERMS) and refuses a
+  // phrase of two or more terms.
+  std::vector<std::vector<DocScore>> ScoreDocsBatch(const std::vector<SearchQuery>& qs,
+                                                    const std::vector<std::vector<int>>& doc_ids) {
+    if (qs.size() != doc_ids.size()) throw std::runtime_error("wiser_hip: one doc id list per query");
+    std::vector<wsr_query> in(qs.size());
+    std::vector<int64_t> off(qs.size() + 1, 0);
+    std::vector<int32_t> docs;
+    for (size_t i = 0; i < qs.size(); ++i) {
+      const SearchQuery& q = qs[i];
+      wsr_query& w = in[i];
+      w = wsr_query{};
+      w.n_terms = static_cast<int32_t>(q.terms.size());
+      w.flags = ((q.is_phrase && q.terms.size() > 1) ? WSR_QUERY_PHRASE : 0) | (q.match_any ? WSR_QUERY_OR : 0);
+      for (size_t t = 0; t < q.terms.size() && t < WSR_MAX_TERMS; ++t) {
+        int32_t df;
+        check(wsr_lookup(h_, q.terms[t].c_str(), &w.list_ids[t], &df));
+      }
+      docs.insert(docs.end(), doc_ids[i].begin(), doc_ids[i].end());
+      off[i + 1] = static_cast<int64_t>(docs.size());
+    }
+    std::vector<wsr_doc_score> flat(docs.size());
+    check(wsr_score_docs(h_, in.data(), static_cast<int32_t>(qs.size()), off.data(), docs.data(), flat.data()));
+    std::vector<std::vector<DocScore>> out(qs.size());
+    for (size_t i = 0; i < qs.size(); ++i)
+      for (int64_t j = off[i]; j < off[i + 1]; ++j) out[i].push_back(DocScore{flat[j].score, flat[j].mask});
+    return out;
+  }
+  std::vector<DocScore> ScoreDocs(const SearchQuery& q, const std::vector<int>& doc_ids) {
+    return ScoreDocsBatch({q}, {doc_ids})[0];
   }
 
   std::vector<SearchResult> SearchBatch(const std::vector<SearchQuery>& qs) {

@@ -51,6 +51,11 @@ class Hit(C.Structure):
     _fields_ = [("doc_id", C.c_int32), ("pad", C.c_int32), ("score", C.c_double)]
 
 
+class DocScore(C.Structure):
+    """wsr_doc_score: what wsr_score_docs answers for one (query, doc) pair"""
+    _fields_ = [("score", C.c_double), ("mask", C.c_uint32), ("pad", C.c_int32)]
+
+
 class BatchStats(C.Structure):
     _fields_ = [("work_items", C.c_uint64), ("survivors", C.c_uint64),
                 ("driver_blocks", C.c_uint64), ("other_blocks", C.c_uint64),
@@ -120,6 +125,8 @@ _sigs = {
                                   C.POINTER(C.c_double)]),
     "wsr_search_batch": (C.c_int, [_P, C.POINTER(Query), C.c_int32, C.c_int32, C.POINTER(Hit),
                                    C.POINTER(C.c_int32)]),
+    "wsr_score_docs": (C.c_int, [_P, C.POINTER(Query), C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                 C.POINTER(DocScore)]),
     "wsr_check_query": (C.c_int, [_P, C.POINTER(Query)]),
     "wsr_resolve_text": (C.c_int, [_P, C.c_char_p, C.c_int64, C.c_int32, C.c_int32, C.POINTER(Query),
                                    C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64]),

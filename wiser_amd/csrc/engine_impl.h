@@ -39,6 +39,16 @@ inline double env_number(const char* name, double dflt) {
 }
 }  // namespace wiser
 
+// What one wsr_score_docs call holds on the device (score_docs.cc): kept in a
+// per-handle pool, one per concurrent caller, as wsr_search_batch's batches.
+struct ScoreCtx {
+  gpu::Stream st;
+  gpu::DevBuf<wiser::ScoreQuery> d_qs;
+  gpu::DevBuf<wiser::ScoreItem> d_items;
+  gpu::DevBuf<uint32_t> d_docs, d_index;
+  gpu::DevBuf<wiser::DocScore> d_out;
+};
+
 struct wsr_handle {
   std::mutex mu;
   int device = 0;
@@ -85,6 +95,8 @@ struct wsr_handle {
   int lean_wgs_ph = 0; // ... its phrase instance's
   int lean_wgs_two = 0; // ... its two-term instance's (one workgroup per CU past residency)
   int gen_cap = 0;     // general workgroups launched at most
+  std::mutex score_mu;                  // wsr_score_docs' reusable contexts
+  std::vector<std::unique_ptr<ScoreCtx>> score_pool;
   // what the upload plan (batch_plan.h) reads of the handle
   wiser::ImageView view() const {
     wiser::ImageView v;

@@ -287,6 +287,29 @@ static_assert(sizeof(OrItem) == 24, "OrItem layout");
 // or_kernel's counters (wsr_or_stats), one u64 each
 enum { kOrStatItems = 0, kOrStatWindows, kOrStatSkipped, kOrStatTouched, kOrStatEvents, kNumOrStats };
 
+// Scoring given (query, doc) pairs (wsr_score_docs): the host sorts each
+// query's candidates by doc id and cuts them into items of at most
+// kScoreLanes consecutive sorted candidates (score_plan.h); score_docs_kernel
+// runs one wave per item, one candidate per lane.
+constexpr uint32_t kScoreLanes = 64;
+struct ScoreQuery {
+  int32_t nt;                // terms of the query (its mask bits)
+  int32_t list[kMaxTerms];   // list id per term, in query order; -1: no postings of it in this image
+};
+static_assert(sizeof(ScoreQuery) == 68, "ScoreQuery layout");
+struct ScoreItem {
+  uint32_t q;       // its query's entry in the ScoreQuery table
+  uint32_t first;   // first of its candidates in the sorted doc and index arrays
+  uint32_t n;       // candidates (1 .. kScoreLanes)
+};
+static_assert(sizeof(ScoreItem) == 12, "ScoreItem layout");
+struct DocScore {   // = wsr_doc_score
+  double score;
+  uint32_t mask;
+  int32_t pad;
+};
+static_assert(sizeof(DocScore) == 16, "DocScore layout");
+
 // A heap-insertion event: a survivor that a top-k heap run from empty over its
 // segment inserts (query_processing.h:595-602).
 struct Event {

@@ -199,4 +199,11 @@ hipError_t launch_or_replay(const OrQuery* oq, uint32_t n_or, const OrItem* item
                             const uint32_t* ev_cnt, HitDev* hits, int hit_stride, int32_t* n_hits,
                             bool narrow, bool wide, hipStream_t st);
 
+// Given (query, doc) pairs (wsr_score_docs): one wave per item of at most
+// kScoreLanes candidates, sorted by doc id at docs[first ..]; the answer of
+// candidate j goes to out[index[j]].  Rows no item covers are left as they are
+// (the caller zeroes out).
+hipError_t launch_score_docs(const IndexArgs& ix, const ScoreQuery* qs, const ScoreItem* items, uint32_t n_items,
+                             const uint32_t* docs, const uint32_t* index, DocScore* out, hipStream_t st);
+
 }  // namespace wiser

@@ -3782,7 +3782,98 @@ __global__ __launch_bounds__(64) void or_replay_kernel(const OrQuery* __restrict
   }
 }
 
+// ------------------------------------------- given (query, doc) pairs --
+// wsr_score_docs: one wave per item, one candidate doc per lane (the item's
+// candidates are sorted by doc id, score_plan.h).  The terms are handled one
+// after the other, in query order, so a lane's sum is or_kernel's: from 0.0,
+// acc = acc + bm25_term per list that holds its doc.  Per term the wave walks
+// the list's blocks: the first lane not yet served holds the smallest doc id
+// still open; find_block moves the cursor to the block that may hold it; the
+// block's doc ids and tfs are decoded into LDS once; every open lane whose doc
+// is at or below the block's last doc searches the 128 ids and is then served
+// (lane `first` among them, so every round serves at least one lane).  The
+// set of open lanes is a ballot, a scalar: the loop control is uniform.
+struct ScoreLds {
+  double norm[256];
+  uint32_t blk[256];   // the current block: 128 doc ids, 128 tfs
+};
+
+__global__ __launch_bounds__(64) void score_docs_kernel(IndexArgs ix, const ScoreQuery* __restrict__ qs,
+                                                        const ScoreItem* __restrict__ items, uint32_t n_items,
+                                                        const uint32_t* __restrict__ docs,
+                                                        const uint32_t* __restrict__ index,
+                                                        DocScore* __restrict__ out) {
+  __shared__ ScoreLds S;
+  const uint32_t l = threadIdx.x & 63;
+  const uint32_t it = blockIdx.x;
+  if (it >= n_items) return;
+  const ScoreItem I = items[it];
+  const uint32_t n = uni(I.n), first = uni(I.first);
+  const ScoreQuery* Q = qs + uni(I.q);
+  const uint32_t nt = uni(static_cast<uint32_t>(Q->nt));
+#pragma unroll
+  for (uint32_t i = 0; i < 4; ++i) S.norm[l + 64 * i] = ix.cache[l + 64 * i];
+  const bool have = l < n;
+  const uint32_t doc = have ? docs[first + l] : 0xFFFFFFFFu;
+  double acc = 0.0;
+  uint32_t mask = 0;
+  __builtin_amdgcn_wave_barrier();
+  for (uint32_t t = 0; t < nt; ++t) {
+    const int32_t id = static_cast<int32_t>(uni(static_cast<uint32_t>(Q->list[t])));
+    if (id < 0) continue;
+    const ListDev L = ix.lists[id];
+    const double idf = L.idf;
+    uint64_t open = __ballot(have);
+    uint32_t cur = 0;
+    while (open) {
+      const uint32_t x = static_cast<uint32_t>(__builtin_amdgcn_readlane(doc, __builtin_ctzll(open)));
+      cur = uni(find_block(ix.blk_last + L.blk0, cur, L.nblk, x));
+      if (cur >= L.nblk) break;   // the list ends below every open doc
+      const uint32_t cnt = cur == L.nblk - 1 ? L.tail_cnt : 128u;
+      if (cur == L.nblk - 1 && L.tail != kNoTail) {   // a VInts last block, decoded at load
+        const uint32_t* tp = ix.tails + L.tail;
+        S.blk[l] = l < cnt ? tp[l] : 0u;
+        S.blk[l + 64] = l + 64 < cnt ? tp[l + 64] : 0u;
+        S.blk[128 + l] = l < cnt ? tp[cnt + l] : 0u;
+        S.blk[192 + l] = l + 64 < cnt ? tp[cnt + l + 64] : 0u;
+        __builtin_amdgcn_wave_barrier();
+      } else {
+        const BlockDev bd = ix.blocks[L.blk0 + cur];
+        const uint32_t m = uni(ix.blk_meta[L.blk0 + cur]);
+        decode_block<true>(ix.blob + L.base + uni(bd.doc_rel), m & 0xFF, cnt, true, uni(bd.prev), S.blk);
+        decode_block<true>(ix.blob + L.base + uni(bd.tf_rel), m >> 8, cnt, false, 0u, S.blk + 128);
+      }
+      const uint32_t last = uni(ix.blk_last[L.blk0 + cur]);
+      const bool mine = ((open >> l) & 1ull) && doc <= last;
+      if (mine) {
+        const uint32_t p = lds_lower_bound(S.blk, cnt, doc);
+        if (p < cnt && S.blk[p] == doc) {
+          const uint32_t c4 = ix.plen[static_cast<uint64_t>(L.blk0 + cur) * 128u + p];
+          acc = acc + bm25_term(idf, S.blk[128 + p], S.norm[c4]);
+          mask |= 1u << t;
+        }
+      }
+      open &= ~__ballot(mine);
+      __builtin_amdgcn_wave_barrier();   // (the next block is decoded over this one)
+    }
+  }
+  if (have) {
+    DocScore r;
+    r.score = acc;
+    r.mask = mask;
+    r.pad = 0;
+    out[index[first + l]] = r;
+  }
+}
+
 // ------------------------------------------------------------ launchers --
+hipError_t launch_score_docs(const IndexArgs& ix, const ScoreQuery* qs, const ScoreItem* items, uint32_t n_items,
+                             const uint32_t* docs, const uint32_t* index, DocScore* out, hipStream_t st) {
+  if (!n_items) return hipSuccess;
+  hipLaunchKernelGGL(score_docs_kernel, dim3(n_items), dim3(64), 0, st, ix, qs, items, n_items, docs, index, out);
+  return hipGetLastError();
+}
+
 hipError_t launch_or_items(const IndexArgs& ix, const OrQuery* oq, const OrItem* items, uint32_t n_items,
                            int nt_max, Event* events, uint32_t* ev_cnt, uint32_t* counters,
                            unsigned long long* stats, hipStream_t st) {

@@ -236,6 +236,42 @@ class VacuumEngine:
                     e.snippet = sn
         return out
 
+    # ---- given (query, doc) pairs -------------------------------------
+    def resolve_terms(self, query: SearchQuery):
+        """-> wsr_query for wsr_score_docs: every term looked up (-1: not in the
+        index, it sets no mask bit), none of Search's empty-result rules; k is
+        ignored there.  The engine checks the term limit and the flags."""
+        q = _capi.Query()
+        q.n_terms = len(query.terms)
+        q.flags = ((_capi.QUERY_PHRASE if (query.is_phrase and len(query.terms) > 1) else 0) |
+                   (_capi.QUERY_OR if query.match_any else 0))
+        for i, t in enumerate(query.terms[:_capi.MAX_TERMS]):
+            q.list_ids[i] = self.lookup(t)[0]
+        return q
+
+    def score_docs_batch(self, queries: Sequence[SearchQuery],
+                         doc_id_lists: Sequence[Sequence[int]]) -> List[List[Tuple[float, int]]]:
+        """wsr_score_docs: per query, (score, mask) of each of its doc ids, in the
+        caller's order.  mask bit t: term t is in the index and its list holds
+        the doc; score: the sum of those terms' BM25, in query order from 0.0
+        (a full mask: the conjunctive score; any mask: the match_any score)."""
+        if len(queries) != len(doc_id_lists):
+            raise ValueError("one doc id list per query")
+        n = len(queries)
+        arr = (_capi.Query * max(n, 1))(*[self.resolve_terms(sq) for sq in queries])
+        off = (C.c_int64 * (n + 1))()
+        for i, d in enumerate(doc_id_lists):
+            off[i + 1] = off[i] + len(d)
+        total = off[n]
+        docs = (C.c_int32 * max(total, 1))(*[int(x) for d in doc_id_lists for x in d])
+        out = (_capi.DocScore * max(total, 1))()
+        check(lib.wsr_score_docs(self._h, arr, n, off, docs, out))
+        return [[(out[j].score, out[j].mask) for j in range(off[i], off[i + 1])] for i in range(n)]
+
+    def score_docs(self, query: SearchQuery, doc_ids: Sequence[int]) -> List[Tuple[float, int]]:
+        """What `query` gives each of doc_ids: [(score, mask)] (score_docs_batch)."""
+        return self.score_docs_batch([query], [doc_ids])[0]
+
     def snippet(self, q, doc_id: int, n_passages: int) -> str:
         """VacuumEngine::GenerateSnippet for result entry doc_id of resolved query q."""
         # (a 1-term phrase query is a plain query in the reference's dispatch)
