@@ -28,6 +28,7 @@ BPLAN   := wiser_amd/_lib/batch_plan_check
 SLAYOUT := wiser_amd/_lib/shard_layout_check
 SPLAN   := wiser_amd/_lib/score_plan_check
 SCLI    := wiser_amd/_lib/score_cli
+BLMIMG  := wiser_amd/_lib/bloom_image_check
 
 # (the buffer owner's, the two plans' and the shard layout's checks are tests of those files
 # alone: a tree whose tests/ does not hold their sources still builds everything else)
@@ -35,11 +36,16 @@ all: $(LIB) $(ORACLE) $(CLI) $(CALIB) $(DICT) $(if $(wildcard tests/cpp/dev_mem_
      $(if $(wildcard tests/cpp/batch_plan_check.cc),$(BPLAN)) \
      $(if $(wildcard tests/cpp/shard_layout_check.cc),$(SLAYOUT)) \
      $(if $(wildcard tests/cpp/score_plan_check.cc),$(SPLAN)) \
-     $(if $(wildcard tests/cpp/score_cli.cc),$(SCLI))
+     $(if $(wildcard tests/cpp/score_cli.cc),$(SCLI)) \
+     $(if $(wildcard tests/cpp/bloom_image_check.cc),$(BLMIMG))
 
 # CPU check of the term dictionary (tests/test_dictionary.py)
 $(DICT): tests/cpp/dict_check.cc wiser_amd/csrc/index.h $(LIB)
 	$(CXX) -O2 -std=c++17 -I/opt/rocm/include -D__HIP_PLATFORM_AMD__ -o $@ tests/cpp/dict_check.cc -Lwiser_amd/_lib -lwiser_hip -Wl,-rpath,'$$ORIGIN'
+
+# CPU check of a shard image's bloom filters against the whole image's (tests/test_bloom_image.py)
+$(BLMIMG): tests/cpp/bloom_image_check.cc wiser_amd/csrc/index.h wiser_amd/csrc/engine_types.h $(LIB)
+	$(CXX) -O2 -std=c++17 -I/opt/rocm/include -D__HIP_PLATFORM_AMD__ -o $@ tests/cpp/bloom_image_check.cc -Lwiser_amd/_lib -lwiser_hip -Wl,-rpath,'$$ORIGIN'
 
 # CPU check of the buffer owner over a fake memory policy (tests/test_dev_mem.py): no HIP, no engine
 $(DEVMEM): tests/cpp/dev_mem_check.cc wiser_amd/csrc/dev_mem.h

@@ -23,12 +23,14 @@ def positions_row(seq):
     return f"t\t{' '.join(seq)}\t{' '.join(toks)}\t{off_col}\t{pos_col}\n"
 
 
-def build_tie_index(root, positions=False):
+def build_tie_index(root, positions=False, bloom=None):
     """20,000 docs built for score ties: doc lengths from four values and tfs
     1..3 of "a" (every doc), "b" (0.8), "c" (0.5) and "d" (0.3), shuffled among
     filler words; doc 7777 holds 300 more "c" (above the 1-byte tf escape).
     positions: the same docs written WITH_POSITIONS (for phrase queries)
-    instead of TOKEN_ONLY.  -> index dir"""
+    instead of TOKEN_ONLY; bloom = (ratio, entries): also with the two-way phrase
+    bloom filters (build_from_linedoc; None: the index as it always was).
+    -> index dir"""
     import wiser_amd as w
     root = str(root)
     path = os.path.join(root, "ties.linedoc")
@@ -51,7 +53,7 @@ def build_tie_index(root, positions=False):
             f.write(positions_row(toks) if positions else f"t\t{' '.join(toks)}\t{' '.join(toks)}\n")
     d = os.path.join(root, "idx")
     os.makedirs(d)
-    w.build_from_linedoc(path, d, "WITH_POSITIONS" if positions else "TOKEN_ONLY")
+    w.build_from_linedoc(path, d, "WITH_POSITIONS" if positions else "TOKEN_ONLY", bloom=bloom)
     return d
 
 
@@ -86,15 +88,17 @@ def write_skewed_linedoc(path, seed):
     return vocab + list(fixed) + ["heavy", "lonely", "absent-term"]
 
 
-def build_skewed_index(root, seed):
-    """write_skewed_linedoc(seed) as a WITH_POSITIONS index -> (index dir, vocabulary)"""
+def build_skewed_index(root, seed, bloom=None):
+    """write_skewed_linedoc(seed) as a WITH_POSITIONS index, with bloom =
+    (ratio, entries) also holding the two-way phrase bloom filters
+    -> (index dir, vocabulary)"""
     import wiser_amd as w
     root = str(root)
     ld = os.path.join(root, "c.linedoc")
     terms = write_skewed_linedoc(ld, seed)
     d = os.path.join(root, "idx")
     os.makedirs(d)
-    w.build_from_linedoc(ld, d, "WITH_POSITIONS")
+    w.build_from_linedoc(ld, d, "WITH_POSITIONS", bloom=bloom)
     return d, terms
 
 

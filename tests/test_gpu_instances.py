@@ -204,19 +204,23 @@ class Lab:
         """More than n docs match the query (the oracle asked for n + 1)."""
         return len(self.expected(corpus, it._replace(k=n + 1))) > n
 
+    def open_engine(self, corpus):
+        """A loaded engine over the corpus's whole index (the mode's environment is set)."""
+        import wiser_amd as w
+        e = w.VacuumEngine(self.index(corpus), positions=POSITIONS[corpus])
+        e.Load()
+        return e
+
     def engine(self, corpus, mode):
         """One engine at a time: the cases are ordered by (corpus, mode)."""
         if self.eng_key != (corpus, mode):
-            import wiser_amd as w
             self.close_engine()
-            d = self.index(corpus)
             saved = {k: os.environ.get(k) for k in ENGINE_ENV}
             try:
                 for k in saved:
                     os.environ.pop(k, None)
                 os.environ.update(ENGINE_MODES[mode])
-                e = w.VacuumEngine(d, positions=POSITIONS[corpus])
-                e.Load()
+                e = self.open_engine(corpus)
             finally:
                 for k, v in saved.items():
                     if v is None:

@@ -16,6 +16,7 @@ import random
 
 import pytest
 
+from bloom_tamper import blank_bloom_boxes
 from conftest import has_phrase, phrase_cases
 from test_gpu_parity import DENSE_MODES, SCORE_RTOL, _engine
 
@@ -165,50 +166,6 @@ def test_bloom_index_loads_and_matches(bloom_indexes, name):
     eng.close()
 
 
-def _varint(b, i):
-    v = sh = 0
-    while True:
-        c = b[i]
-        i += 1
-        v |= (c & 0x7F) << sh
-        sh += 7
-        if not c & 0x80:
-            return v, i
-
-
-def _blank_first_bloom_boxes(d, terms):
-    """Mark every posting of the first bloom box of `terms` (both sections) as
-    having no filter: the box's presence bitmap zeroed in place (the arrays stay
-    but nothing points at them).  The reference's reader then answers "not
-    present" for those postings (flash_iterators.h:1045-1050)."""
-    import struct
-    tip = open(os.path.join(d, "my.tip"), "rb").read()
-    offs, at = {}, 0
-    while at < len(tip):
-        n = struct.unpack_from("<I", tip, at)[0]
-        t = tip[at + 4:at + 4 + n].decode()
-        v = struct.unpack_from("<q", tip, at + 4 + n)[0]
-        offs[t] = v & ((1 << 48) - 1)
-        at += 4 + n + 8
-    vac = bytearray(open(os.path.join(d, "my.vacuum"), "rb").read())
-    for t in terms:
-        o = offs[t]
-        assert vac[o] == 0xF4
-        _, i = _varint(vac, o + 1)
-        s0, i = _varint(vac, i)
-        s1, _ = _varint(vac, i)
-        for s in (s0, s1):
-            p = o + s
-            assert vac[p] == 0xA4
-            _, p = _varint(vac, p + 1)
-            first, _ = _varint(vac, p)
-            b = o + first
-            assert vac[b] == 0xF5
-            n, q = _varint(vac, b + 1)
-            vac[q:q + (n + 7) // 8] = bytes((n + 7) // 8)
-    open(os.path.join(d, "my.vacuum"), "wb").write(bytes(vac))
-
-
 @pytest.mark.parametrize("factor", [0, 1, 3])
 def test_bloom_pruning_follows_reference(bloom_indexes, tmp_path, factor):
     """The GPU applies IsPossibleToPresent (query_processing.h:873-884) before
@@ -224,7 +181,7 @@ def test_bloom_pruning_follows_reference(bloom_indexes, tmp_path, factor):
     d = str(tmp_path / "tampered")
     shutil.copytree(src, d)
     heads = [f"w{i}" for i in range(8)]
-    _blank_first_bloom_boxes(d, heads)
+    blank_bloom_boxes(d, {t: [0] for t in heads})
     ld = os.path.join(os.path.dirname(plain), "pos.linedoc")
     seqs = [l.rstrip("\n").split("\t")[1].split() for l in open(ld).readlines()[1:]]
     rng = random.Random(97)

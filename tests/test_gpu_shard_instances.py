@@ -147,17 +147,20 @@ class ShardLab(Lab):
             self.cuts[corpus, cut] = [tuple(r) for r in rgs]
         return self.cuts[corpus, cut]
 
+    def open_shard_engines(self, corpus, rgs):
+        """The loaded shard engines of the tiling rgs (the mode's environment is set)."""
+        return open_shards(self.index(corpus), len(rgs), positions=POSITIONS[corpus], ranges=rgs)
+
     def shards(self, corpus, cut, mode):
         if self.sh_key != (corpus, cut, mode):
             self.close_shards()
             rgs = self.ranges(corpus, cut)
-            d = self.index(corpus)
             saved = {k: os.environ.get(k) for k in ENGINE_ENV}
             try:
                 for k in saved:
                     os.environ.pop(k, None)
                 os.environ.update(ENGINE_MODES[mode])
-                self.sh = open_shards(d, len(rgs), positions=POSITIONS[corpus], ranges=rgs)
+                self.sh = self.open_shard_engines(corpus, rgs)
             finally:
                 for k, v in saved.items():
                     if v is None:

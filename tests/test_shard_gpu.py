@@ -17,9 +17,10 @@ from conftest import DATA
 pytestmark = pytest.mark.gpu
 
 
-def open_shards(index_dir, world, positions=False, ranges=None):
+def open_shards(index_dir, world, positions=False, ranges=None, bloom_factor=1):
     """The W shard engines of a doc-range split of index_dir (ranges: a
-    hand-made tiling of [0, n_docs) instead of the even split)."""
+    hand-made tiling of [0, n_docs) instead of the even split; bloom_factor:
+    VacuumEngine's, which matters on an index written with bloom filters)."""
     import wiser_amd as w
     from wiser_amd.shard import index_doc_count, shard_range
     n = index_doc_count(index_dir)
@@ -28,7 +29,7 @@ def open_shards(index_dir, world, positions=False, ranges=None):
     engs = []
     try:
         for rg in ranges:
-            e = w.VacuumEngine(index_dir, doc_range=tuple(rg), positions=positions)
+            e = w.VacuumEngine(index_dir, doc_range=tuple(rg), positions=positions, bloom_factor=bloom_factor)
             e.Load()
             engs.append(e)
     except Exception:
