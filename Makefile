@@ -9,6 +9,7 @@ ORACLE  := oracle/_build/liboracle.so
 SRCS    := wiser_amd/csrc/writer.cc wiser_amd/csrc/index.cc wiser_amd/csrc/engine.cc \
            wiser_amd/csrc/shard_exchange.cc wiser_amd/csrc/batch_plan.cc wiser_amd/csrc/server.cc \
            wiser_amd/csrc/score_plan.cc wiser_amd/csrc/score_docs.cc \
+           wiser_amd/csrc/bool_plan.cc wiser_amd/csrc/bool_search.cc \
            wiser_amd/csrc/docstore.cc \
            wiser_amd/csrc/snippet.cc wiser_amd/csrc/kernels.hip
 HDRS    := $(wildcard wiser_amd/csrc/*.h) include/wiser_hip.h
@@ -29,6 +30,8 @@ SLAYOUT := wiser_amd/_lib/shard_layout_check
 SPLAN   := wiser_amd/_lib/score_plan_check
 SCLI    := wiser_amd/_lib/score_cli
 BLMIMG  := wiser_amd/_lib/bloom_image_check
+BOPLAN  := wiser_amd/_lib/bool_plan_check
+BOCLI   := wiser_amd/_lib/bool_cli
 
 # (the buffer owner's, the two plans' and the shard layout's checks are tests of those files
 # alone: a tree whose tests/ does not hold their sources still builds everything else)
@@ -37,7 +40,9 @@ all: $(LIB) $(ORACLE) $(CLI) $(CALIB) $(DICT) $(if $(wildcard tests/cpp/dev_mem_
      $(if $(wildcard tests/cpp/shard_layout_check.cc),$(SLAYOUT)) \
      $(if $(wildcard tests/cpp/score_plan_check.cc),$(SPLAN)) \
      $(if $(wildcard tests/cpp/score_cli.cc),$(SCLI)) \
-     $(if $(wildcard tests/cpp/bloom_image_check.cc),$(BLMIMG))
+     $(if $(wildcard tests/cpp/bloom_image_check.cc),$(BLMIMG)) \
+     $(if $(wildcard tests/cpp/bool_plan_check.cc),$(BOPLAN)) \
+     $(if $(wildcard tests/cpp/bool_cli.cc),$(BOCLI))
 
 # CPU check of the term dictionary (tests/test_dictionary.py)
 $(DICT): tests/cpp/dict_check.cc wiser_amd/csrc/index.h $(LIB)
@@ -54,6 +59,7 @@ $(DEVMEM): tests/cpp/dev_mem_check.cc wiser_amd/csrc/dev_mem.h
 
 # CPU check of the upload plan on a hand-made image (tests/test_batch_plan.py): no HIP, no engine
 $(BPLAN): tests/cpp/batch_plan_check.cc wiser_amd/csrc/batch_plan.cc wiser_amd/csrc/batch_plan.h \
+          wiser_amd/csrc/or_plan.h \
           wiser_amd/csrc/engine_types.h include/wiser_hip.h
 	@mkdir -p wiser_amd/_lib
 	$(CXX) -O2 -std=c++17 -Wall -o $@ tests/cpp/batch_plan_check.cc wiser_amd/csrc/batch_plan.cc
@@ -70,6 +76,12 @@ $(SPLAN): tests/cpp/score_plan_check.cc wiser_amd/csrc/score_plan.cc wiser_amd/c
 	@mkdir -p wiser_amd/_lib
 	$(CXX) -O2 -std=c++17 -Wall -o $@ tests/cpp/score_plan_check.cc wiser_amd/csrc/score_plan.cc
 
+# CPU check of the wsr_search_bool plan on a hand-made image (tests/test_bool_plan.py): no HIP, no engine
+$(BOPLAN): tests/cpp/bool_plan_check.cc wiser_amd/csrc/bool_plan.cc wiser_amd/csrc/bool_plan.h \
+           wiser_amd/csrc/or_plan.h wiser_amd/csrc/batch_plan.h wiser_amd/csrc/engine_types.h include/wiser_hip.h
+	@mkdir -p wiser_amd/_lib
+	$(CXX) -O2 -std=c++17 -Wall -o $@ tests/cpp/bool_plan_check.cc wiser_amd/csrc/bool_plan.cc
+
 # counter calibration (profiles only): known-byte reads for rocprofv3 --pmc
 $(CALIB): scripts/calib_ea.hip
 	@mkdir -p wiser_amd/_lib
@@ -81,6 +93,10 @@ $(CLI): tests/cpp/engine_cli.cc include/wiser_hip_engine.hpp include/wiser_hip.h
 # C++ host of the (query, doc) scoring mirror (tests/test_gpu_score_docs.py)
 $(SCLI): tests/cpp/score_cli.cc include/wiser_hip_engine.hpp include/wiser_hip.h $(LIB)
 	$(CXX) -O2 -std=c++17 -Iinclude -o $@ tests/cpp/score_cli.cc -Lwiser_amd/_lib -lwiser_hip -Wl,-rpath,'$$ORIGIN'
+
+# C++ host of the boolean query mirror (tests/test_gpu_bool.py)
+$(BOCLI): tests/cpp/bool_cli.cc include/wiser_hip_engine.hpp include/wiser_hip.h $(LIB)
+	$(CXX) -O2 -std=c++17 -Iinclude -o $@ tests/cpp/bool_cli.cc -Lwiser_amd/_lib -lwiser_hip -Wl,-rpath,'$$ORIGIN'
 
 $(OBJDIR)/%.o: wiser_amd/csrc/% $(HDRS)
 	@mkdir -p $(OBJDIR)

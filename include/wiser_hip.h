@@ -254,6 +254,61 @@ typedef struct wsr_doc_score {
 int wsr_score_docs(wsr_handle* h, const wsr_query* q, int32_t nq, const int64_t* doc_off,
                    const int32_t* docs, wsr_doc_score* out);
 
+/* Boolean queries (beyond the reference): each term is required (MUST), adds
+ * to the score when present (SHOULD) or excludes the doc (MUST_NOT), and at
+ * least min_should of the SHOULD terms have to be present.
+ *
+ * Match.  Let S(d) be the number of SHOULD term slots whose list holds d (a
+ * term given twice is two slots).  Doc d matches iff every MUST term's list
+ * holds d, no MUST_NOT term's list holds d, and
+ * S(d) >= max(min_should, 1 if the query has no MUST term else 0).
+ * Score.  From 0.0, for each MUST or SHOULD slot in query order whose list
+ * holds d, score = score + the BM25 term: the operations of every other path,
+ * without FMA.  MUST_NOT slots add nothing.
+ * Rank.  RankDoc over the matching docs in ascending doc id, then SortHeap, as
+ * for every query.
+ * Missing terms (list id -1): a missing MUST term gives an empty result, a
+ * missing SHOULD term is a slot that never holds, a missing MUST_NOT term
+ * excludes nothing.
+ * Empty results, not errors: min_should above the number of resolvable SHOULD
+ * slots, a query of MUST_NOT terms only, n_terms = 0, k <= 0.
+ * Identities, bit for bit and ties included: all roles MUST gives
+ * wsr_search_batch's conjunctive result for the same terms; all roles SHOULD
+ * with min_should <= 1 gives the WSR_QUERY_OR result.
+ * Errors, all checked on the host before anything is enqueued (a refused call
+ * writes neither hits nor n_hits): n_terms > WSR_MAX_OR_TERMS, k > WSR_MAX_K
+ * and k > hit_stride are WSR_E_LIMIT; a role outside 0..2, min_should < 0,
+ * n_terms < 0, a list id below -1 or past the index, nq < 0 and null arguments
+ * with nq > 0 are WSR_E_INVALID.
+ * Calling.  hits: nq * hit_stride entries, n_hits[q] = entries written for
+ * query q (the rest of a row is zero).  Synchronous; may be called concurrently
+ * on one handle; nq = 0 is fine.  On a doc-range shard engine the call answers
+ * over the image's doc range, as wsr_search_batch does.  Boolean queries take
+ * no part in doc-range shard steps, the micro-batching server, snippets or the
+ * text log format. */
+enum { WSR_ROLE_SHOULD = 0, WSR_ROLE_MUST = 1, WSR_ROLE_MUST_NOT = 2 };
+typedef struct wsr_bool_query {
+  int32_t n_terms;                       /* 0 .. WSR_MAX_OR_TERMS */
+  int32_t k;                             /* n_results; <= 0 => empty result */
+  int32_t list_ids[WSR_MAX_OR_TERMS];    /* from wsr_lookup, in query order; -1 = not in the index */
+  uint8_t role[WSR_MAX_OR_TERMS];        /* WSR_ROLE_* per term */
+  int32_t min_should;                    /* >= 0 */
+} wsr_bool_query;
+int wsr_search_bool(wsr_handle* h, const wsr_bool_query* q, int32_t nq, int32_t hit_stride,
+                    wsr_hit* hits, int32_t* n_hits);
+/* The per-query checks of wsr_search_bool alone (not k against a hit stride):
+ * WSR_OK or the code the call would return. */
+int wsr_check_bool_query(wsr_handle* h, const wsr_bool_query* q);
+/* wsr_search_bool with two knobs for tests and measurements: item_blocks > 0
+ * cuts the queries into work items of about that many blocks (0: the engine's
+ * default, as wsr_batch_set_item_blocks), and stats, when not NULL, receives
+ * the call's counters in wsr_or_stats' terms (windows_skipped only counts
+ * queries without a MUST term: with one, windows are started by its lead list
+ * alone).  All 0 when no query of the call reached the device. */
+struct wsr_or_stats;
+int wsr_search_bool_ex(wsr_handle* h, const wsr_bool_query* q, int32_t nq, int32_t hit_stride,
+                       wsr_hit* hits, int32_t* n_hits, int32_t item_blocks, struct wsr_or_stats* stats);
+
 /* Queries as text, the reference's query-log format (QueryProducerByLog,
  * query_pool.h:319-378): one query per line, terms separated by spaces, a
  * line in double quotes is a phrase query.  Every term is resolved through the

@@ -12,6 +12,7 @@
 #include <map>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "wiser_hip.h"
@@ -50,6 +51,14 @@ struct SearchResult {  // types.h:297-346
 struct DocScore {  // what a query gives one doc (ScoreDocs; beyond the reference)
   double score = 0;
   uint32_t mask = 0;   // bit t: term t is in the index and its list holds the doc
+};
+
+enum class Role { kShould = WSR_ROLE_SHOULD, kMust = WSR_ROLE_MUST, kMustNot = WSR_ROLE_MUST_NOT };
+
+struct BoolQuery {  // wsr_bool_query by term strings (SearchBool; beyond the reference)
+  std::vector<std::pair<std::string, Role>> terms;   // in query order, at most WSR_MAX_OR_TERMS
+  int n_results = 10;
+  int min_should = 0;   // SHOULD terms a doc has to hold at least (1 when no term is MUST)
 };
 
 inline void check(int rc) {
@@ -136,6 +145,48 @@ class VacuumHipEngine {
   }
   std::vector<DocScore> ScoreDocs(const SearchQuery& q, const std::vector<int>& doc_ids) {
     return ScoreDocsBatch({q}, {doc_ids})[0];
+  }
+
+  // wsr_search_bool: MUST / SHOULD / MUST_NOT terms with min_should.  Entries
+  // and doc_freqs as for a match_any query: a term missing from the index has
+  // doc_freq 0 (a missing MUST term: no entries); no terms or n_results <= 0:
+  // nothing, doc_freqs unset.  The engine checks the limits.
+  std::vector<SearchResult> SearchBool(const std::vector<BoolQuery>& qs) {
+    std::vector<wsr_bool_query> in(qs.size());
+    std::vector<std::vector<int>> freqs(qs.size());
+    int stride = 1;
+    for (size_t i = 0; i < qs.size(); ++i) {
+      const BoolQuery& q = qs[i];
+      if (q.terms.size() > WSR_MAX_OR_TERMS)
+        throw std::runtime_error("wiser_hip: more than WSR_MAX_OR_TERMS terms in a boolean query");
+      wsr_bool_query& w = in[i];
+      w = wsr_bool_query{};
+      w.n_terms = static_cast<int32_t>(q.terms.size());
+      w.k = q.n_results < 0 ? 0 : q.n_results;
+      w.min_should = q.min_should;
+      for (size_t t = 0; t < q.terms.size(); ++t) {
+        int32_t df;
+        check(wsr_lookup(h_, q.terms[t].first.c_str(), &w.list_ids[t], &df));
+        w.role[t] = static_cast<uint8_t>(q.terms[t].second);
+        freqs[i].push_back(df);
+      }
+      if (w.k > stride) stride = w.k;
+    }
+    std::vector<wsr_hit> hits(qs.size() * stride);
+    std::vector<int32_t> nh(qs.size());
+    check(wsr_search_bool(h_, in.data(), static_cast<int32_t>(qs.size()), stride, hits.data(), nh.data()));
+    std::vector<SearchResult> out(qs.size());
+    for (size_t i = 0; i < qs.size(); ++i) {
+      if (qs[i].terms.empty() || in[i].k == 0) continue;
+      out[i].doc_freqs = freqs[i];
+      for (int j = 0; j < nh[i]; ++j) {
+        SearchResultEntry e;
+        e.doc_id = hits[i * stride + j].doc_id;
+        e.doc_score = hits[i * stride + j].score;
+        out[i].entries.push_back(e);
+      }
+    }
+    return out;
   }
 
   std::vector<SearchResult> SearchBatch(const std::vector<SearchQuery>& qs) {

@@ -56,6 +56,16 @@ class DocScore(C.Structure):
     _fields_ = [("score", C.c_double), ("mask", C.c_uint32), ("pad", C.c_int32)]
 
 
+ROLE_SHOULD, ROLE_MUST, ROLE_MUST_NOT = 0, 1, 2     # wsr_bool_query.role
+ROLES = {"should": ROLE_SHOULD, "must": ROLE_MUST, "must_not": ROLE_MUST_NOT}
+
+
+class BoolQuery(C.Structure):
+    """wsr_bool_query: MUST / SHOULD / MUST_NOT terms with min_should (wsr_search_bool)"""
+    _fields_ = [("n_terms", C.c_int32), ("k", C.c_int32), ("list_ids", C.c_int32 * MAX_OR_TERMS),
+                ("role", C.c_uint8 * MAX_OR_TERMS), ("min_should", C.c_int32)]
+
+
 class BatchStats(C.Structure):
     _fields_ = [("work_items", C.c_uint64), ("survivors", C.c_uint64),
                 ("driver_blocks", C.c_uint64), ("other_blocks", C.c_uint64),
@@ -128,6 +138,11 @@ _sigs = {
     "wsr_score_docs": (C.c_int, [_P, C.POINTER(Query), C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                                  C.POINTER(DocScore)]),
     "wsr_check_query": (C.c_int, [_P, C.POINTER(Query)]),
+    "wsr_search_bool": (C.c_int, [_P, C.POINTER(BoolQuery), C.c_int32, C.c_int32, C.POINTER(Hit),
+                                  C.POINTER(C.c_int32)]),
+    "wsr_check_bool_query": (C.c_int, [_P, C.POINTER(BoolQuery)]),
+    "wsr_search_bool_ex": (C.c_int, [_P, C.POINTER(BoolQuery), C.c_int32, C.c_int32, C.POINTER(Hit),
+                                     C.POINTER(C.c_int32), C.c_int32, C.POINTER(OrStats)]),
     "wsr_resolve_text": (C.c_int, [_P, C.c_char_p, C.c_int64, C.c_int32, C.c_int32, C.POINTER(Query),
                                    C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64]),
     "wsr_search_text": (C.c_int, [_P, C.c_char_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,

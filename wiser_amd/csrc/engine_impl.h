@@ -49,6 +49,21 @@ struct ScoreCtx {
   gpu::DevBuf<wiser::DocScore> d_out;
 };
 
+// What one wsr_search_bool call holds on the device (bool_search.cc): kept in
+// a per-handle pool, one per concurrent caller, as the ScoreCtx.
+struct BoolCtx {
+  gpu::Stream st;
+  gpu::DevBuf<wiser::OrQuery> d_qs;
+  gpu::DevBuf<wiser::BoolRoles> d_roles;     // (sized together with d_qs)
+  gpu::DevBuf<wiser::OrItem> d_items;
+  gpu::DevBuf<uint32_t> d_evcnt;             // (sized together with d_items)
+  gpu::DevBuf<wiser::Event> d_events;
+  gpu::DevBuf<uint32_t> d_ctr;               // kNumCounters (the error flags)
+  gpu::DevBuf<unsigned long long> d_stats;   // kNumOrStats
+  gpu::DevBuf<wiser::HitDev> d_hits;
+  gpu::DevBuf<int32_t> d_nhits;
+};
+
 struct wsr_handle {
   std::mutex mu;
   int device = 0;
@@ -97,6 +112,8 @@ struct wsr_handle {
   int gen_cap = 0;     // general workgroups launched at most
   std::mutex score_mu;                  // wsr_score_docs' reusable contexts
   std::vector<std::unique_ptr<ScoreCtx>> score_pool;
+  std::mutex bool_mu;                   // wsr_search_bool's reusable contexts
+  std::vector<std::unique_ptr<BoolCtx>> bool_pool;
   // what the upload plan (batch_plan.h) reads of the handle
   wiser::ImageView view() const {
     wiser::ImageView v;

@@ -287,6 +287,21 @@ static_assert(sizeof(OrItem) == 24, "OrItem layout");
 // or_kernel's counters (wsr_or_stats), one u64 each
 enum { kOrStatItems = 0, kOrStatWindows, kOrStatSkipped, kOrStatTouched, kOrStatEvents, kNumOrStats };
 
+// Boolean queries (wsr_search_bool): the OR traversal plus, per doc, which
+// term slots held it, and a predicate on that record.  A query's device record
+// is an OrQuery (its resolved slots in query order, what or_replay_kernel
+// reads, and the MaxScore sums over its MUST and SHOULD slots; a MUST_NOT
+// slot's is 0.0) and, at the same place of a second table, its BoolRoles.
+// Slots that can never hold a doc (a SHOULD or MUST_NOT term that is missing
+// or has no block in the image) are dropped by the host, so the masks are over
+// the resolved slots; need_should keeps counting the query's own slots.
+struct BoolRoles {
+  uint32_t must_mask, should_mask, not_mask;   // bit t: resolved slot t's role
+  uint32_t need_should;   // SHOULD slots that must hold a doc: max(min_should, no MUST term ? 1 : 0)
+  int32_t lead;           // the MUST slot with the fewest blocks in the image (-1: no MUST term)
+};
+static_assert(sizeof(BoolRoles) == 20, "BoolRoles layout");
+
 // Scoring given (query, doc) pairs (wsr_score_docs): the host sorts each
 // query's candidates by doc id and cuts them into items of at most
 // kScoreLanes consecutive sorted candidates (score_plan.h); score_docs_kernel

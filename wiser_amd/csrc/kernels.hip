@@ -3782,6 +3782,259 @@ __global__ __launch_bounds__(64) void or_replay_kernel(const OrQuery* __restrict
   }
 }
 
+// ------------------------------------------------------------ boolean --
+// wsr_search_bool: or_kernel's traversal (one wave per item, windows of
+// kOrWindow docs, the terms one after the other in query order, each slot's
+// current block decoded in LDS) with one more record per doc of the window:
+// held, a bit per slot whose list holds the doc.  A MUST or SHOULD slot adds
+// its BM25 term to the accumulator exactly as or_kernel does (wave barrier
+// between terms, first add 0.0 + x) and sets its bit; a MUST_NOT slot sets its
+// bit and marks the doc touched, so that the touched-docs pass clears the
+// record -- it decodes no tf, reads no plen and adds nothing.  The touched
+// docs pass in doc order, and a doc reaches the running top-k (EventFilter;
+// the event slot for k > kMaxK) only when it holds every MUST slot, no
+// MUST_NOT slot and at least need_should SHOULD slots; a dropped doc's lane is
+// not valid to the filter and leaves its state alone.
+//
+// Which lists start windows.  With a MUST term, the lead slot alone: a matching
+// doc is one of its postings.  Without one, or_kernel's MaxScore rule over the
+// SHOULD slots with the same margin: theta is the k-th best of the matching
+// docs this item has passed to the filter, the reference heap at that doc has
+// seen those docs and more, and a doc that holds only non-essential slots
+// scores at most their summed bound, which is below theta -- it is never an
+// insertion, whether or not it matches.  MUST_NOT slots carry no bound and are
+// never essential; they are read inside the windows the others start.
+struct BoolLds {
+  double acc[kOrWindow];
+  uint32_t bits[kOrWindow / 32];
+  uint32_t held[kOrWindow / 2];   // 16 bits per doc (two docs per word): bit t = slot t's list holds it
+  double norm[256];
+  Event evs[64];
+  uint32_t cur[kMaxOrTerms];      // per term slot: first block of its list not wholly consumed
+  uint32_t cached[kMaxOrTerms];   // ... the block decoded in its cache row (kNoBlock: none)
+};
+static_assert(kMaxOrTerms <= 16, "bool_kernel: a doc's held record is 16 bits");
+
+__global__ __launch_bounds__(64) void bool_kernel(IndexArgs ix, const OrQuery* __restrict__ oqs,
+                                                  const BoolRoles* __restrict__ roles,
+                                                  const OrItem* __restrict__ items, uint32_t n_items,
+                                                  Event* __restrict__ events, uint32_t* __restrict__ ev_cnt,
+                                                  uint32_t* __restrict__ counters,
+                                                  unsigned long long* __restrict__ stats) {
+  __shared__ BoolLds S;
+  // per term slot the current block of its list, decoded: 128 doc ids, 128 tfs
+  extern __shared__ uint32_t or_cache[];
+  const uint32_t l = threadIdx.x & 63;
+  const uint32_t it = blockIdx.x;
+  if (it >= n_items) return;
+  const OrItem I = items[it];
+  const OrQuery* Q = oqs + I.oq;
+  const BoolRoles R = roles[I.oq];
+  const uint32_t nt = uni(static_cast<uint32_t>(Q->nt));
+  const uint32_t k = uni(static_cast<uint32_t>(Q->k));
+  const uint32_t must = uni(R.must_mask), should = uni(R.should_mask), nots = uni(R.not_mask);
+  const uint32_t need = uni(R.need_should);
+  const bool led = must != 0u;   // the lead slot alone starts windows
+  const bool wide = k > static_cast<uint32_t>(kMaxK);   // every matching doc is an event
+  const uint32_t dhi = uni(I.doc_hi), ev_cap = uni(I.ev_cap);
+  Event* ev_out = events + I.ev_base;
+#pragma unroll
+  for (uint32_t i = 0; i < 4; ++i) S.norm[l + 64 * i] = ix.cache[l + 64 * i];
+  for (uint32_t i = l; i < kOrWindow; i += 64) S.acc[i] = 0.0;
+  for (uint32_t i = l; i < kOrWindow / 2; i += 64) S.held[i] = 0u;
+  S.bits[l] = 0u;
+  if (l < static_cast<uint32_t>(kMaxOrTerms)) {
+    S.cur[l] = 0u;
+    S.cached[l] = kNoBlock;
+  }
+  const double ubsum = l < nt ? Q->ubsum[l] : 0.0;
+  uint32_t ess = led ? 1u << uni(static_cast<uint32_t>(R.lead)) : should;   // the slots that start windows
+  __builtin_amdgcn_wave_barrier();
+
+  // block c of list L decoded in slot t's cache row (its tfs too: with_tf); its posting count
+  auto load_block = [&](uint32_t t, const ListDev& L, uint32_t c, bool with_tf) __attribute__((always_inline)) {
+    const uint32_t cnt = c == L.nblk - 1 ? L.tail_cnt : 128u;
+    if (uni(S.cached[t]) == c) return cnt;
+    uint32_t* d = or_cache + t * 256u;
+    __builtin_amdgcn_wave_barrier();
+    if (c == L.nblk - 1 && L.tail != kNoTail) {   // a VInts last block, decoded at load
+      const uint32_t* tp = ix.tails + L.tail;
+      d[l] = l < cnt ? tp[l] : 0u;
+      d[l + 64] = l + 64 < cnt ? tp[l + 64] : 0u;
+      if (with_tf) {
+        d[128 + l] = l < cnt ? tp[cnt + l] : 0u;
+        d[192 + l] = l + 64 < cnt ? tp[cnt + l + 64] : 0u;
+      }
+    } else {
+      const BlockDev bd = ix.blocks[L.blk0 + c];
+      const uint32_t m = uni(ix.blk_meta[L.blk0 + c]);
+      decode_block<true>(ix.blob + L.base + uni(bd.doc_rel), m & 0xFF, cnt, true, uni(bd.prev), d);
+      if (with_tf) decode_block<true>(ix.blob + L.base + uni(bd.tf_rel), m >> 8, cnt, false, 0u, d + 128);
+    }
+    if (l == 0) S.cached[t] = c;
+    __builtin_amdgcn_wave_barrier();
+    return cnt;
+  };
+  // slot t's cursor moved to the first block with a doc >= x
+  auto advance = [&](uint32_t t, const ListDev& L, uint32_t x) __attribute__((always_inline)) {
+    const uint32_t c = uni(find_block(ix.blk_last + L.blk0, uni(S.cur[t]), L.nblk, x));
+    __builtin_amdgcn_wave_barrier();
+    if (l == 0) S.cur[t] = c;
+    __builtin_amdgcn_wave_barrier();
+    return c;
+  };
+
+  EventFilter F;
+  F.k = k;
+  uint32_t ev_n = 0, evb = 0;
+  bool over = false;
+  uint32_t n_win = 0, n_skip = 0, n_touch = 0;
+  auto flush = [&]() __attribute__((always_inline)) {
+    __builtin_amdgcn_wave_barrier();
+    if (ev_n <= ev_cap) {
+      if (l < evb) ev_out[ev_n - evb + l] = S.evs[l];
+    } else {
+      over = true;
+    }
+    __builtin_amdgcn_wave_barrier();
+    evb = 0;
+  };
+  auto emit = [&](double sv, int32_t dv) __attribute__((always_inline)) {
+    if (evb == 64u) flush();
+    if (l == 0) {
+      Event e;
+      e.score = sv;
+      e.doc = dv;
+      e.pad = 0;
+      S.evs[evb] = e;
+    }
+    ++ev_n;
+    ++evb;
+  };
+
+  uint32_t pos = uni(I.doc_lo);   // docs below pos are consumed
+  while (pos < dhi) {
+    // the smallest unconsumed doc id over the window-starting lists
+    uint32_t next = dhi;
+    uint32_t ne_end = 0;   // (statistics) one past the last doc of the non-essential SHOULD lists still open
+    for (uint32_t t = 0; t < nt; ++t) {
+      const ListDev L = ix.lists[Q->list[t]];
+      const uint32_t c = advance(t, L, pos);
+      if (c >= L.nblk) continue;
+      if (!((ess >> t) & 1u)) {
+        if (!led && ((should >> t) & 1u)) ne_end = umax(ne_end, L.last + 1u);
+        continue;
+      }
+      if (uni(ix.blocks[L.blk0 + c].prev) >= next) continue;   // its docs lie past `next`
+      const uint32_t cnt = load_block(t, L, c, true);
+      const uint32_t* d = or_cache + t * 256u;
+      // (the block's last doc is >= pos: the count of docs below pos is < cnt)
+      const uint32_t below = __popcll(__ballot(l < cnt && d[l] < pos)) +
+                             __popcll(__ballot(l + 64 < cnt && d[l + 64] < pos));
+      const uint32_t first = uni(d[below < cnt ? below : cnt - 1]);
+      next = first < next ? first : next;
+    }
+    next = umax(next, pos);   // (every window ends past pos)
+    const uint32_t wb = next & ~(kOrWindow - 1u);
+    const uint32_t lo = umax(wb, pos);
+    {
+      // windows jumped over while a non-essential SHOULD list still had postings
+      const uint32_t to = next >= dhi ? dhi : lo;
+      const uint32_t end = to < ne_end ? to : ne_end;
+      if (end > pos) n_skip += (end - pos + kOrWindow - 1u) / kOrWindow;
+    }
+    if (next >= dhi) break;
+    const uint32_t hi = dhi - wb > kOrWindow ? wb + kOrWindow : dhi;
+    ++n_win;
+    for (uint32_t t = 0; t < nt; ++t) {
+      const ListDev L = ix.lists[Q->list[t]];
+      uint32_t c = advance(t, L, lo);
+      const double idf = L.idf;
+      const bool excl = (nots >> t) & 1u;   // a MUST_NOT slot: membership alone
+      const uint32_t tbit = 1u << t;
+      while (c < L.nblk) {
+        if (uni(ix.blocks[L.blk0 + c].prev) >= hi) break;   // the block starts past the window
+        const uint32_t cnt = load_block(t, L, c, !excl);
+        const uint32_t* d = or_cache + t * 256u;
+        const uint8_t* pl = ix.plen + static_cast<uint64_t>(L.blk0 + c) * 128u;
+#pragma unroll
+        for (uint32_t j = l; j < 128u; j += 64u) {
+          const uint32_t doc = d[j];
+          if (j < cnt && doc >= lo && doc < hi) {
+            const uint32_t i = doc - wb;
+            if (!excl) S.acc[i] = S.acc[i] + bm25_term(idf, d[128 + j], S.norm[pl[j]]);
+            // (two docs share a word of held: the lanes of one term may meet there)
+            atomicOr(&S.held[i >> 1], tbit << (16u * (i & 1u)));
+            atomicOr(&S.bits[i >> 5], 1u << (i & 31u));
+          }
+        }
+        if (uni(ix.blk_last[L.blk0 + c]) >= hi) break;   // it goes on in the next window
+        ++c;
+      }
+      __builtin_amdgcn_wave_barrier();
+      if (l == 0) S.cur[t] = c;
+      __builtin_amdgcn_wave_barrier();   // (and the next term's adds come after this term's)
+    }
+    // the touched docs, in doc order: chunk ch = docs wb + 64 * ch + lane
+    const uint32_t w = S.bits[l];
+    uint64_t nz = __ballot(w != 0u);
+    while (nz) {
+      const uint32_t ch = static_cast<uint32_t>(__builtin_ctzll(nz)) >> 1;
+      nz &= ~(3ull << (2u * ch));
+      // (readlane returns an int: through uint32_t, or the low word's bit 31 would sign-extend)
+      const uint32_t m_lo = static_cast<uint32_t>(__builtin_amdgcn_readlane(w, static_cast<int>(2u * ch)));
+      const uint32_t m_hi = static_cast<uint32_t>(__builtin_amdgcn_readlane(w, static_cast<int>(2u * ch + 1u)));
+      const uint64_t m = (static_cast<uint64_t>(m_hi) << 32) | m_lo;
+      const bool touched = (m >> l) & 1ull;
+      const uint32_t i = 64u * ch + l;
+      const double sc = S.acc[i];
+      const uint32_t h = (S.held[i >> 1] >> (16u * (i & 1u))) & 0xFFFFu;
+      const int32_t doc = static_cast<int32_t>(wb + i);
+      n_touch += __popcll(m);
+      const bool match = touched && (h & must) == must && (h & nots) == 0u &&
+                         static_cast<uint32_t>(__popc(h & should)) >= need;
+      __builtin_amdgcn_wave_barrier();   // (every lane has read its half of a held word)
+      if (l < 32u) S.held[32u * ch + l] = 0u;
+      if (touched) S.acc[i] = 0.0;
+      if (wide) {
+        const uint64_t mm = __ballot(match);
+        const uint32_t n = __popcll(mm);
+        if (ev_n + n <= ev_cap) {
+          if (match) {
+            Event e;
+            e.score = sc;
+            e.doc = doc;
+            e.pad = 0;
+            ev_out[ev_n + __popcll(mm & lanemask_lt())] = e;
+          }
+        } else {
+          over = true;
+        }
+        ev_n += n;
+      } else {
+        F.step(sc, doc, match, emit);
+      }
+    }
+    S.bits[l] = 0u;
+    __builtin_amdgcn_wave_barrier();
+    pos = hi;
+    if (!led && !wide && F.pt_n >= k) {
+      const double thr = readlane_f64(F.pt, static_cast<int>(k) - 1) * kOrMargin;
+      ess = static_cast<uint32_t>(__ballot(l < nt && !(ubsum <= thr))) & should;
+    }
+  }
+  if (evb) flush();
+  if (l == 0) {
+    ev_cnt[it] = over ? 0u : ev_n;
+    if (over) atomicOr(&counters[kCtrError], static_cast<uint32_t>(kErrCapacity));
+    atomicAdd(&stats[kOrStatItems], 1ull);
+    atomicAdd(&stats[kOrStatWindows], static_cast<unsigned long long>(n_win));
+    atomicAdd(&stats[kOrStatSkipped], static_cast<unsigned long long>(n_skip));
+    atomicAdd(&stats[kOrStatTouched], static_cast<unsigned long long>(n_touch));
+    atomicAdd(&stats[kOrStatEvents], static_cast<unsigned long long>(ev_n));
+  }
+}
+
 // ------------------------------------------- given (query, doc) pairs --
 // wsr_score_docs: one wave per item, one candidate doc per lane (the item's
 // candidates are sorted by doc id, score_plan.h).  The terms are handled one
@@ -3880,6 +4133,15 @@ hipError_t launch_or_items(const IndexArgs& ix, const OrQuery* oq, const OrItem*
   if (!n_items) return hipSuccess;
   hipLaunchKernelGGL(or_kernel, dim3(n_items), dim3(64), sizeof(uint32_t) * 256u * static_cast<uint32_t>(nt_max),
                      st, ix, oq, items, n_items, events, ev_cnt, counters, stats);
+  return hipGetLastError();
+}
+
+hipError_t launch_bool_items(const IndexArgs& ix, const OrQuery* oq, const BoolRoles* roles, const OrItem* items,
+                             uint32_t n_items, int nt_max, Event* events, uint32_t* ev_cnt, uint32_t* counters,
+                             unsigned long long* stats, hipStream_t st) {
+  if (!n_items) return hipSuccess;
+  hipLaunchKernelGGL(bool_kernel, dim3(n_items), dim3(64), sizeof(uint32_t) * 256u * static_cast<uint32_t>(nt_max),
+                     st, ix, oq, roles, items, n_items, events, ev_cnt, counters, stats);
   return hipGetLastError();
 }
 

@@ -49,6 +49,19 @@ class SearchQuery:
 
 
 @dataclass
+class BoolQuery:
+    """A boolean query (beyond the reference, wsr_search_bool): terms is
+    [(term, role)] in query order, role one of "must", "should", "must_not".
+    A doc matches when it holds every must term, no must_not term and at least
+    max(min_should, 1 if there is no must term else 0) of the should terms (a
+    term given twice counts twice); its score is the sum of the BM25 terms of
+    the must and should terms it holds, in query order."""
+    terms: List[Tuple[str, str]]
+    n_results: int = 10
+    min_should: int = 0
+
+
+@dataclass
 class SearchResultEntry:
     """types.h:259-274 (snippet filled when the query asks for snippets)"""
     doc_id: int
@@ -234,6 +247,53 @@ class VacuumEngine:
             for a, i in enumerate(idx):
                 for e, sn in zip(out[i].entries, snips[a]):
                     e.snippet = sn
+        return out
+
+    # ---- boolean queries ------------------------------------------------
+    def resolve_bool(self, query: BoolQuery):
+        """-> (wsr_bool_query, doc_freqs or None): every term looked up (-1: not
+        in the index, its doc_freq 0); doc_freqs None as for match_any (no terms
+        or n_results <= 0).  The engine checks the limits."""
+        if len(query.terms) > _capi.MAX_OR_TERMS:
+            raise _capi.WiserError(_capi.E_LIMIT, f"more than {_capi.MAX_OR_TERMS} terms in a boolean query")
+        q = _capi.BoolQuery()
+        q.n_terms = len(query.terms)
+        q.k = max(0, int(query.n_results))
+        q.min_should = int(query.min_should)
+        dfs = []
+        for i, (t, role) in enumerate(query.terms):
+            if role not in _capi.ROLES:
+                raise ValueError(f"role {role!r}: one of {sorted(_capi.ROLES)}")
+            lid, df = self.lookup(t)
+            q.list_ids[i] = lid
+            q.role[i] = _capi.ROLES[role]
+            dfs.append(df)
+        return q, (None if (not dfs or q.k == 0) else dfs)
+
+    def search_bool(self, queries: Sequence[BoolQuery]) -> List[SearchResult]:
+        """wsr_search_bool: one SearchResult per query, entries ordered as every
+        query's, doc_freqs as for Search with match_any (0 for a missing term)."""
+        if not queries:
+            return []
+        n = len(queries)
+        arr = (_capi.BoolQuery * n)()
+        freqs = []
+        stride = 1
+        for i, bq in enumerate(queries):
+            arr[i], f = self.resolve_bool(bq)
+            freqs.append(f)
+            stride = max(stride, arr[i].k)
+        hits = (_capi.Hit * (n * stride))()
+        nh = (C.c_int32 * n)()
+        check(lib.wsr_search_bool(self._h, arr, n, stride, hits, nh))
+        out = []
+        for i in range(n):
+            r = SearchResult()
+            if freqs[i] is not None:
+                r.doc_freqs = list(freqs[i])
+                r.entries = [SearchResultEntry(hits[i * stride + j].doc_id, hits[i * stride + j].score)
+                             for j in range(nh[i])]
+            out.append(r)
         return out
 
     # ---- given (query, doc) pairs -------------------------------------
