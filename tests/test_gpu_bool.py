@@ -132,6 +132,22 @@ def test_bool_identities(synth_ctx):   # noqa: F811
             assert sum(len(g) for g in got) > 0
 
 
+@pytest.mark.parametrize("item_blocks", [63, 1])
+def test_bool_all_should_is_or(tie_ctx, skip_ctx, item_blocks):   # noqa: F811
+    """bool_kernel and or_kernel are two instances of one traversal: an
+    all-SHOULD wsr_search_bool_ex call and the same queries as WSR_QUERY_OR in
+    one resident batch give equal hits and equal counters, all five."""
+    for ctx, terms in ((tie_ctx, [["a", "b"], ["b", "a"], ["c", "d"], ["a", "b", "c", "d"]]),
+                       (skip_ctx, [["common", "rare"], ["rare", "common"]])):
+        qs = [(t, k) for t in terms for k in (10, 65)]
+        want, ost = ctx.run(qs, item_blocks)
+        got, bst = run_bool(ctx.eng, [([(x, S) for x in t], 0, k) for t, k in qs], item_blocks)
+        assert got == want and all(want)
+        for f in ("items", "windows", "windows_skipped", "touched_docs", "events"):
+            assert getattr(bst, f) == getattr(ost, f), (f, getattr(bst, f), getattr(ost, f))
+        assert ost.items > 0 and ost.events > 0
+
+
 # ---- the suite's fixtures, through both mirrors ----------------------------------------
 FIXTURE_QUERIES = {
     "three": [q("+hello world"), q("hello +world -big"), q("wisconsin big"), q("-hello world"), q("hello world", 2),

@@ -73,23 +73,9 @@ int plan_bool(const ImageView& v, const wsr_bool_query* q, int32_t nq, int32_t s
         r.lead = t;
     const size_t item0 = p.items.size();
     const uint64_t ev0 = p.ev_total;
-    // (the cut is over all kept slots, MUST_NOT lists included: their blocks are read too; the sums
-    // plan_or_query leaves in oq.ubsum count every slot and are replaced below)
-    plan_or_query(v, target, &oq, &p.items, &p.ev_total);
-    // MaxScore bounds over the scoring slots alone, summed in ascending (bound, slot) order
-    int by[kMaxOrTerms];
-    int ns = 0;
-    for (int t = 0; t < oq.nt; ++t) {
-      oq.ubsum[t] = 0.0;
-      if (!((r.not_mask >> t) & 1u)) by[ns++] = t;
-    }
-    auto ub = [&](int t) { return 2.2 * v.lists[oq.list[t]].idf; };
-    std::stable_sort(by, by + ns, [&](int a, int c) { return ub(a) < ub(c); });
-    double sum = 0.0;
-    for (int k = 0; k < ns; ++k) {
-      sum += ub(by[k]);
-      oq.ubsum[by[k]] = sum;
-    }
+    // (the cut is over all kept slots, MUST_NOT lists included: their blocks are read too; the
+    // MaxScore bounds are over the scoring slots alone)
+    plan_or_query(v, target, &oq, &p.items, &p.ev_total, ~r.not_mask);
     if (r.lead >= 0) {
       // a matching doc is a posting of the lead list
       const ListDev& L = v.lists[oq.list[r.lead]];

@@ -38,14 +38,7 @@ extern "C" int wsr_search_bool_ex(wsr_handle* h, const wsr_bool_query* q, int32_
   }
   const size_t n_q = p.qs.size(), n_items = p.items.size();
   if (n_items > 0xFFFFFFFFull) return fail(WSR_E_LIMIT, "over 2^32 boolean work items");
-  std::unique_ptr<BoolCtx> c;
-  {
-    std::lock_guard<std::mutex> g(h->bool_mu);
-    if (!h->bool_pool.empty()) {
-      c = std::move(h->bool_pool.back());
-      h->bool_pool.pop_back();
-    }
-  }
+  std::unique_ptr<BoolCtx> c = h->bool_pool.take();
   uint32_t ctr[kNumCounters];
   unsigned long long sv[kNumOrStats];
   try {
@@ -84,18 +77,9 @@ extern "C" int wsr_search_bool_ex(wsr_handle* h, const wsr_bool_query* q, int32_
     if (c && c->st) (void)hipStreamSynchronize(c->st);
     return fail(WSR_E_HIP, e.what());
   }
-  {
-    std::lock_guard<std::mutex> g(h->bool_mu);
-    if (h->bool_pool.size() < 8) h->bool_pool.push_back(std::move(c));
-  }
+  h->bool_pool.give(std::move(c));
   if (ctr[kCtrError]) return fail(WSR_E_INTERNAL, "device reported error flags " + std::to_string(ctr[kCtrError]));
-  if (stats) {
-    stats->items = sv[kOrStatItems];
-    stats->windows = sv[kOrStatWindows];
-    stats->windows_skipped = sv[kOrStatSkipped];
-    stats->touched_docs = sv[kOrStatTouched];
-    stats->events = sv[kOrStatEvents];
-  }
+  if (stats) *stats = or_stats_of(sv);
   return WSR_OK;
 }
 

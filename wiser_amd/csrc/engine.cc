@@ -892,11 +892,7 @@ int wsr_batch_or_stats_get(wsr_handle* h, wsr_batch* b, wsr_or_stats* out) {
     HIP_OK(hipStreamSynchronize(b->st));
     unsigned long long v[kNumOrStats];
     HIP_OK(hipMemcpy(v, b->d_orstat, sizeof v, hipMemcpyDeviceToHost));
-    out->items = v[kOrStatItems];
-    out->windows = v[kOrStatWindows];
-    out->windows_skipped = v[kOrStatSkipped];
-    out->touched_docs = v[kOrStatTouched];
-    out->events = v[kOrStatEvents];
+    *out = or_stats_of(v);
   } catch (const std::exception& e) {
     return fail(WSR_E_HIP, e.what());
   }

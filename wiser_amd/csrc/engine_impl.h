@@ -37,7 +37,41 @@ inline double env_number(const char* name, double dflt) {
   const double x = std::strtod(v, &end);
   return (end && *end == 0 && x >= 0) ? x : dflt;
 }
+
+// the traversal kernels' kNumOrStats counters as the C ABI's record
+inline wsr_or_stats or_stats_of(const unsigned long long* v) {
+  wsr_or_stats s{};
+  s.items = v[kOrStatItems];
+  s.windows = v[kOrStatWindows];
+  s.windows_skipped = v[kOrStatSkipped];
+  s.touched_docs = v[kOrStatTouched];
+  s.events = v[kOrStatEvents];
+  return s;
+}
 }  // namespace wiser
+
+// A handle's reusable per-call contexts, one per concurrent caller.
+template <class T>
+class CtxPool {
+ public:
+  // an idle context, or null: the caller makes one
+  std::unique_ptr<T> take() {
+    std::lock_guard<std::mutex> g(mu_);
+    if (idle_.empty()) return nullptr;
+    std::unique_ptr<T> c = std::move(idle_.back());
+    idle_.pop_back();
+    return c;
+  }
+  // back after a call that went well (at most 8 are kept)
+  void give(std::unique_ptr<T> c) {
+    std::lock_guard<std::mutex> g(mu_);
+    if (idle_.size() < 8) idle_.push_back(std::move(c));
+  }
+
+ private:
+  std::mutex mu_;
+  std::vector<std::unique_ptr<T>> idle_;
+};
 
 // What one wsr_score_docs call holds on the device (score_docs.cc): kept in a
 // per-handle pool, one per concurrent caller, as wsr_search_batch's batches.
@@ -110,10 +144,8 @@ struct wsr_handle {
   int lean_wgs_ph = 0; // ... its phrase instance's
   int lean_wgs_two = 0; // ... its two-term instance's (one workgroup per CU past residency)
   int gen_cap = 0;     // general workgroups launched at most
-  std::mutex score_mu;                  // wsr_score_docs' reusable contexts
-  std::vector<std::unique_ptr<ScoreCtx>> score_pool;
-  std::mutex bool_mu;                   // wsr_search_bool's reusable contexts
-  std::vector<std::unique_ptr<BoolCtx>> bool_pool;
+  CtxPool<ScoreCtx> score_pool;         // wsr_score_docs' reusable contexts
+  CtxPool<BoolCtx> bool_pool;           // wsr_search_bool's
   // what the upload plan (batch_plan.h) reads of the handle
   wiser::ImageView view() const {
     wiser::ImageView v;

@@ -199,9 +199,9 @@ hipError_t launch_or_replay(const OrQuery* oq, uint32_t n_or, const OrItem* item
                             const uint32_t* ev_cnt, HitDev* hits, int hit_stride, int32_t* n_hits,
                             bool narrow, bool wide, hipStream_t st);
 
-// Boolean queries (wsr_search_bool): or_kernel's traversal with, per doc of
-// the window, the set of slots that held it; a touched doc reaches the item's
-// running top-k (or its event slot, k > kMaxK) only if it satisfies roles[q]
+// Boolean queries (wsr_search_bool): or_kernel's traversal body (window_item),
+// instantiated with, per doc of the window, the set of slots that held it; a
+// touched doc reaches the item's running top-k (or its event slot, k > kMaxK) only if it satisfies roles[q]
 // (engine_types.h, BoolRoles).  oq[i] and roles[i] describe one query; the
 // events are replayed by launch_or_replay over the same oq table.
 hipError_t launch_bool_items(const IndexArgs& ix, const OrQuery* oq, const BoolRoles* roles, const OrItem* items,

@@ -3509,32 +3509,92 @@ __device__ __noinline__ void owner_replay_tail(const QueryIn* qs, const int32_t*
     owner_replay_query<false>(qs, static_cast<int>(qi), b0, ns, meta, ms, st, recv, hits, hs, n_hits, counters);
 }
 
-// ------------------------------------------------------- disjunctive (OR) --
-// One wave per item (a doc-id range of the image, cut by the host).  The
-// range is walked in windows of kOrWindow docs, aligned to kOrWindow: an f64
-// accumulator per doc and a touched bitmap in LDS.  Per window the terms are
-// handled one after the other, in query order: the blocks of the term's list
-// that overlap the window are decoded (each list's current block stays
-// decoded in LDS, so a block that spans several windows is decoded once), and
-// every posting inside the window adds bm25_term(idf, tf, norm[plen]) to its
-// doc's accumulator.  Doc ids are unique within a list, so the adds of one
+// ------------------------------------- disjunctive (OR) and boolean --
+// the postings of block c of list L
+__device__ __forceinline__ uint32_t block_count(const ListDev& L, uint32_t c) {
+  return c == L.nblk - 1 ? L.tail_cnt : 128u;
+}
+
+// Block c of list L decoded into dst: 128 doc ids, then (with_tf) 128 tfs, from
+// the last block's VInts tail, decoded at load, or from the packed block.
+// Returns the block's posting count; ends with a wave barrier.
+__device__ __forceinline__ uint32_t load_list_block(const IndexArgs& ix, const ListDev& L, uint32_t c, bool with_tf,
+                                                    uint32_t* dst) {
+  const uint32_t l = threadIdx.x & 63;
+  const uint32_t cnt = block_count(L, c);
+  if (c == L.nblk - 1 && L.tail != kNoTail) {
+    const uint32_t* tp = ix.tails + L.tail;
+    dst[l] = l < cnt ? tp[l] : 0u;
+    dst[l + 64] = l + 64 < cnt ? tp[l + 64] : 0u;
+    if (with_tf) {
+      dst[128 + l] = l < cnt ? tp[cnt + l] : 0u;
+      dst[192 + l] = l + 64 < cnt ? tp[cnt + l + 64] : 0u;
+    }
+    __builtin_amdgcn_wave_barrier();
+  } else {
+    const BlockDev bd = ix.blocks[L.blk0 + c];
+    const uint32_t m = uni(ix.blk_meta[L.blk0 + c]);
+    decode_block<true>(ix.blob + L.base + uni(bd.doc_rel), m & 0xFF, cnt, true, uni(bd.prev), dst);
+    if (with_tf) decode_block<true>(ix.blob + L.base + uni(bd.tf_rel), m >> 8, cnt, false, 0u, dst + 128);
+  }
+  return cnt;
+}
+
+// The windowed traversal of or_kernel (WSR_QUERY_OR) and bool_kernel
+// (wsr_search_bool): window_item<kBool>, one wave per item (a doc-id range of
+// the image, cut by the host).  The range is walked in windows of kOrWindow
+// docs, aligned to kOrWindow: an f64 accumulator per doc and a touched bitmap
+// in LDS.  Per window the terms are handled one after the other, in query
+// order: the blocks of the term's list that overlap the window are decoded
+// (each list's current block stays decoded in LDS, so a block that spans
+// several windows is decoded once), and every posting inside the window adds
+// bm25_term(idf, tf, norm[plen]) to its doc's accumulator.
+//
+// The accumulator order.  Doc ids are unique within a list, so the adds of one
 // term never meet; a wave barrier between terms fixes the order of the
 // additions to the query's term order, and the first add is 0.0 + x (exact):
 // a doc's sum is the reference's left-to-right f64 sum over the terms it holds.
 // The touched docs then pass, in doc order, through the item's running top-k
-// (EventFilter; every touched doc for k > kMaxK) into the item's event slot.
+// (EventFilter) into the item's event slot.
+//
+// The event slot.  Events are buffered 64 at a time in LDS; for k > kMaxK there
+// is no filter and every passing doc is written straight to the slot.  An item
+// whose events outgrow the slot the host sized (ev_cap) writes none past it,
+// reports no events and raises kErrCapacity.
 //
 // MaxScore (k <= kMaxK): a term's score is below 2.2 * idf.  Once the running
 // top-k is full, the terms whose bounds -- summed in ascending order -- stay at
-// or below 0.998 times its k-th best are non-essential: a doc that holds only
-// such terms scores at most that sum, which is below the k-th best of the
+// or below kOrMargin times its k-th best are non-essential: a doc that holds
+// only such terms scores at most that sum, which is below the k-th best of the
 // item's own docs so far and so not above the reference heap's minimum at
 // that doc (the heap has seen those docs and more): it is never an insertion,
 // and the filter would drop it unchanged.  Non-essential terms therefore stop
 // starting windows -- the next window is the one of the smallest unconsumed
 // doc id over the essential lists -- and are still accumulated inside the
 // windows the others start.
-struct OrLds {
+//
+// The OR instance has no role table: no MUST and no MUST_NOT slot, every slot
+// SHOULD, and "holds at least one" is "touched".  The boolean instance
+// (everything under `if constexpr (kBool)`) keeps one more record per doc of
+// the window: held, a bit per slot whose list holds the doc.  A MUST_NOT slot
+// sets its bit and marks the doc touched, so that the touched-docs pass clears
+// the record -- it decodes no tf, reads no plen and adds nothing.  A touched
+// doc reaches the filter only when it holds every MUST slot, no MUST_NOT slot
+// and at least need_should SHOULD slots; a dropped doc's lane is not valid to
+// the filter and leaves its state alone.  With a MUST term the lead slot alone
+// starts windows (a matching doc is one of its postings).  Without one,
+// MaxScore runs over the SHOULD slots: theta is the k-th best of the matching
+// docs passed to the filter, and the argument above holds whether or not the
+// doc that holds only non-essential slots matches.  MUST_NOT slots carry no
+// bound and are never essential.
+template <bool kBool>
+struct WindowHeld {
+  uint32_t held[kOrWindow / 2];   // 16 bits per doc (two docs per word): bit t = slot t's list holds it
+};
+template <>
+struct WindowHeld<false> {};   // (the OR instance's LDS carries no held)
+template <bool kBool>
+struct WindowLds : WindowHeld<kBool> {
   double acc[kOrWindow];
   uint32_t bits[kOrWindow / 32];
   double norm[256];
@@ -3542,58 +3602,59 @@ struct OrLds {
   uint32_t cur[kMaxOrTerms];      // per term slot: first block of its list not wholly consumed
   uint32_t cached[kMaxOrTerms];   // ... the block decoded in its cache row (kNoBlock: none)
 };
-static_assert(kOrWindow == 2048, "or_kernel: one bitmap word per lane");
+static_assert(kOrWindow == 2048, "window_item: one bitmap word per lane");
+static_assert(kMaxOrTerms <= 16, "window_item: a doc's held record is 16 bits");
+static_assert(sizeof(WindowLds<false>) + sizeof(WindowHeld<true>) == sizeof(WindowLds<true>), "held alone differs");
 constexpr double kOrMargin = 0.998;   // the pre-probe pruning's margin
 
-__global__ __launch_bounds__(64) void or_kernel(IndexArgs ix, const OrQuery* __restrict__ oqs,
-                                                const OrItem* __restrict__ items, uint32_t n_items,
-                                                Event* __restrict__ events, uint32_t* __restrict__ ev_cnt,
-                                                uint32_t* __restrict__ counters,
-                                                unsigned long long* __restrict__ stats) {
-  __shared__ OrLds S;
-  // per term slot the current block of its list, decoded: 128 doc ids, 128 tfs
-  extern __shared__ uint32_t or_cache[];
+// cache: per term slot the current block of its list, decoded (128 doc ids, 128 tfs)
+template <bool kBool>
+__device__ __forceinline__ void window_item(WindowLds<kBool>& S, uint32_t* cache, const IndexArgs& ix,
+                                            const OrQuery* __restrict__ oqs, const BoolRoles* __restrict__ roles,
+                                            const OrItem* __restrict__ items, uint32_t it,
+                                            Event* __restrict__ events, uint32_t* __restrict__ ev_cnt,
+                                            uint32_t* __restrict__ counters,
+                                            unsigned long long* __restrict__ stats) {
   const uint32_t l = threadIdx.x & 63;
-  const uint32_t it = blockIdx.x;
-  if (it >= n_items) return;
   const OrItem I = items[it];
   const OrQuery* Q = oqs + I.oq;
   const uint32_t nt = uni(static_cast<uint32_t>(Q->nt));
   const uint32_t k = uni(static_cast<uint32_t>(Q->k));
-  const bool wide = k > static_cast<uint32_t>(kMaxK);   // every touched doc is an event
+  const bool wide = k > static_cast<uint32_t>(kMaxK);   // every passing doc is an event
   const uint32_t dhi = uni(I.doc_hi), ev_cap = uni(I.ev_cap);
   Event* ev_out = events + I.ev_base;
+  BoolRoles R{};
+  if constexpr (kBool) R = roles[I.oq];
 #pragma unroll
   for (uint32_t i = 0; i < 4; ++i) S.norm[l + 64 * i] = ix.cache[l + 64 * i];
   for (uint32_t i = l; i < kOrWindow; i += 64) S.acc[i] = 0.0;
+  if constexpr (kBool)
+    for (uint32_t i = l; i < kOrWindow / 2; i += 64) S.held[i] = 0u;
   S.bits[l] = 0u;
   if (l < static_cast<uint32_t>(kMaxOrTerms)) {
     S.cur[l] = 0u;
     S.cached[l] = kNoBlock;
   }
   const double ubsum = l < nt ? Q->ubsum[l] : 0.0;
-  const uint32_t all = (1u << nt) - 1u;
-  uint32_t ess = all;   // essential term slots
+  uint32_t ess = (1u << nt) - 1u;   // the slots that start windows
+  uint32_t must = 0u, should = 0u, nots = 0u, need = 0u;
+  bool led = false;   // the lead slot alone starts windows
+  if constexpr (kBool) {
+    must = uni(R.must_mask);
+    should = uni(R.should_mask);
+    nots = uni(R.not_mask);
+    need = uni(R.need_should);
+    led = must != 0u;
+    ess = led ? 1u << uni(static_cast<uint32_t>(R.lead)) : should;
+  }
   __builtin_amdgcn_wave_barrier();
 
-  // block c of list L decoded in slot t's cache row; its posting count
-  auto load_block = [&](uint32_t t, const ListDev& L, uint32_t c) __attribute__((always_inline)) {
-    const uint32_t cnt = c == L.nblk - 1 ? L.tail_cnt : 128u;
+  // block c of list L decoded in slot t's cache row (its tfs too: with_tf); its posting count
+  auto load_block = [&](uint32_t t, const ListDev& L, uint32_t c, bool with_tf) __attribute__((always_inline)) {
+    const uint32_t cnt = block_count(L, c);
     if (uni(S.cached[t]) == c) return cnt;
-    uint32_t* d = or_cache + t * 256u;
     __builtin_amdgcn_wave_barrier();
-    if (c == L.nblk - 1 && L.tail != kNoTail) {   // a VInts last block, decoded at load
-      const uint32_t* tp = ix.tails + L.tail;
-      d[l] = l < cnt ? tp[l] : 0u;
-      d[l + 64] = l + 64 < cnt ? tp[l + 64] : 0u;
-      d[128 + l] = l < cnt ? tp[cnt + l] : 0u;
-      d[192 + l] = l + 64 < cnt ? tp[cnt + l + 64] : 0u;
-    } else {
-      const BlockDev bd = ix.blocks[L.blk0 + c];
-      const uint32_t m = uni(ix.blk_meta[L.blk0 + c]);
-      decode_block<true>(ix.blob + L.base + uni(bd.doc_rel), m & 0xFF, cnt, true, uni(bd.prev), d);
-      decode_block<true>(ix.blob + L.base + uni(bd.tf_rel), m >> 8, cnt, false, 0u, d + 128);
-    }
+    load_list_block(ix, L, c, with_tf, cache + t * 256u);
     if (l == 0) S.cached[t] = c;
     __builtin_amdgcn_wave_barrier();
     return cnt;
@@ -3639,18 +3700,20 @@ __global__ __launch_bounds__(64) void or_kernel(IndexArgs ix, const OrQuery* __r
   while (pos < dhi) {
     // the smallest unconsumed doc id over the essential lists
     uint32_t next = dhi;
-    uint32_t ne_end = 0;   // (statistics) one past the last doc of the non-essential lists still open
+    uint32_t ne_end = 0;   // (statistics) one past the last doc of the non-essential SHOULD lists still open
     for (uint32_t t = 0; t < nt; ++t) {
       const ListDev L = ix.lists[Q->list[t]];
       const uint32_t c = advance(t, L, pos);
       if (c >= L.nblk) continue;
       if (!((ess >> t) & 1u)) {
-        ne_end = umax(ne_end, L.last + 1u);
+        bool scoring = true;   // (MaxScore set it aside, not its role)
+        if constexpr (kBool) scoring = !led && ((should >> t) & 1u);
+        if (scoring) ne_end = umax(ne_end, L.last + 1u);
         continue;
       }
       if (uni(ix.blocks[L.blk0 + c].prev) >= next) continue;   // its docs lie past `next`
-      const uint32_t cnt = load_block(t, L, c);
-      const uint32_t* d = or_cache + t * 256u;
+      const uint32_t cnt = load_block(t, L, c, true);
+      const uint32_t* d = cache + t * 256u;
       // (the block's last doc is >= pos: the count of docs below pos is < cnt)
       const uint32_t below = __popcll(__ballot(l < cnt && d[l] < pos)) +
                              __popcll(__ballot(l + 64 < cnt && d[l + 64] < pos));
@@ -3661,7 +3724,7 @@ __global__ __launch_bounds__(64) void or_kernel(IndexArgs ix, const OrQuery* __r
     const uint32_t wb = next & ~(kOrWindow - 1u);
     const uint32_t lo = umax(wb, pos);
     {
-      // windows jumped over while a non-essential list still had postings
+      // windows jumped over while a non-essential SHOULD list still had postings
       const uint32_t to = next >= dhi ? dhi : lo;
       const uint32_t end = to < ne_end ? to : ne_end;
       if (end > pos) n_skip += (end - pos + kOrWindow - 1u) / kOrWindow;
@@ -3673,17 +3736,21 @@ __global__ __launch_bounds__(64) void or_kernel(IndexArgs ix, const OrQuery* __r
       const ListDev L = ix.lists[Q->list[t]];
       uint32_t c = advance(t, L, lo);
       const double idf = L.idf;
+      bool excl = false;   // a MUST_NOT slot: membership alone
+      if constexpr (kBool) excl = (nots >> t) & 1u;
       while (c < L.nblk) {
         if (uni(ix.blocks[L.blk0 + c].prev) >= hi) break;   // the block starts past the window
-        const uint32_t cnt = load_block(t, L, c);
-        const uint32_t* d = or_cache + t * 256u;
+        const uint32_t cnt = load_block(t, L, c, !excl);
+        const uint32_t* d = cache + t * 256u;
         const uint8_t* pl = ix.plen + static_cast<uint64_t>(L.blk0 + c) * 128u;
 #pragma unroll
         for (uint32_t j = l; j < 128u; j += 64u) {
           const uint32_t doc = d[j];
           if (j < cnt && doc >= lo && doc < hi) {
             const uint32_t i = doc - wb;
-            S.acc[i] = S.acc[i] + bm25_term(idf, d[128 + j], S.norm[pl[j]]);
+            if (!excl) S.acc[i] = S.acc[i] + bm25_term(idf, d[128 + j], S.norm[pl[j]]);
+            // (two docs share a word of held: the lanes of one term may meet there)
+            if constexpr (kBool) atomicOr(&S.held[i >> 1], (1u << t) << (16u * (i & 1u)));
             atomicOr(&S.bits[i >> 5], 1u << (i & 31u));
           }
         }
@@ -3708,32 +3775,43 @@ __global__ __launch_bounds__(64) void or_kernel(IndexArgs ix, const OrQuery* __r
       const uint32_t i = 64u * ch + l;
       const double sc = S.acc[i];
       const int32_t doc = static_cast<int32_t>(wb + i);
-      const uint32_t n = __popcll(m);
-      n_touch += n;
+      n_touch += __popcll(m);
+      bool match = touched;   // the doc passes to the filter
+      if constexpr (kBool) {
+        const uint32_t h = (S.held[i >> 1] >> (16u * (i & 1u))) & 0xFFFFu;
+        match = touched && (h & must) == must && (h & nots) == 0u &&
+                static_cast<uint32_t>(__popc(h & should)) >= need;
+        __builtin_amdgcn_wave_barrier();   // (every lane has read its half of a held word)
+        if (l < 32u) S.held[32u * ch + l] = 0u;
+      }
+      if (touched) S.acc[i] = 0.0;   // (sc is read: cleared for the next window)
       if (wide) {
+        uint64_t mm = m;   // the chunk's passing docs
+        if constexpr (kBool) mm = __ballot(match);
+        const uint32_t n = __popcll(mm);
         if (ev_n + n <= ev_cap) {
-          if (touched) {
+          if (match) {
             Event e;
             e.score = sc;
             e.doc = doc;
             e.pad = 0;
-            ev_out[ev_n + __popcll(m & lanemask_lt())] = e;
+            ev_out[ev_n + __popcll(mm & lanemask_lt())] = e;
           }
         } else {
           over = true;
         }
         ev_n += n;
       } else {
-        F.step(sc, doc, touched, emit);
+        F.step(sc, doc, match, emit);
       }
-      if (touched) S.acc[i] = 0.0;
     }
     S.bits[l] = 0u;
     __builtin_amdgcn_wave_barrier();
     pos = hi;
-    if (!wide && F.pt_n >= k) {
+    if (!led && !wide && F.pt_n >= k) {
       const double thr = readlane_f64(F.pt, static_cast<int>(k) - 1) * kOrMargin;
       ess = static_cast<uint32_t>(__ballot(l < nt && !(ubsum <= thr)));
+      if constexpr (kBool) ess &= should;
     }
   }
   if (evb) flush();
@@ -3746,6 +3824,29 @@ __global__ __launch_bounds__(64) void or_kernel(IndexArgs ix, const OrQuery* __r
     atomicAdd(&stats[kOrStatTouched], static_cast<unsigned long long>(n_touch));
     atomicAdd(&stats[kOrStatEvents], static_cast<unsigned long long>(ev_n));
   }
+}
+
+__global__ __launch_bounds__(64) void or_kernel(IndexArgs ix, const OrQuery* __restrict__ oqs,
+                                                const OrItem* __restrict__ items, uint32_t n_items,
+                                                Event* __restrict__ events, uint32_t* __restrict__ ev_cnt,
+                                                uint32_t* __restrict__ counters,
+                                                unsigned long long* __restrict__ stats) {
+  __shared__ WindowLds<false> S;
+  extern __shared__ uint32_t or_cache[];
+  if (blockIdx.x >= n_items) return;
+  window_item<false>(S, or_cache, ix, oqs, nullptr, items, blockIdx.x, events, ev_cnt, counters, stats);
+}
+
+__global__ __launch_bounds__(64) void bool_kernel(IndexArgs ix, const OrQuery* __restrict__ oqs,
+                                                  const BoolRoles* __restrict__ roles,
+                                                  const OrItem* __restrict__ items, uint32_t n_items,
+                                                  Event* __restrict__ events, uint32_t* __restrict__ ev_cnt,
+                                                  uint32_t* __restrict__ counters,
+                                                  unsigned long long* __restrict__ stats) {
+  __shared__ WindowLds<true> S;
+  extern __shared__ uint32_t or_cache[];
+  if (blockIdx.x >= n_items) return;
+  window_item<true>(S, or_cache, ix, oqs, roles, items, blockIdx.x, events, ev_cnt, counters, stats);
 }
 
 // One wave per OR query: the events of its items (doc-id order) through the
@@ -3779,259 +3880,6 @@ __global__ __launch_bounds__(64) void or_replay_kernel(const OrQuery* __restrict
     sink.k = k;
     consume_stream<false>(sink, n, count_of, base_of, [](double, int32_t) {});
     sink.finish(hits + qi * hit_stride, &n_hits[qi]);
-  }
-}
-
-// ------------------------------------------------------------ boolean --
-// wsr_search_bool: or_kernel's traversal (one wave per item, windows of
-// kOrWindow docs, the terms one after the other in query order, each slot's
-// current block decoded in LDS) with one more record per doc of the window:
-// held, a bit per slot whose list holds the doc.  A MUST or SHOULD slot adds
-// its BM25 term to the accumulator exactly as or_kernel does (wave barrier
-// between terms, first add 0.0 + x) and sets its bit; a MUST_NOT slot sets its
-// bit and marks the doc touched, so that the touched-docs pass clears the
-// record -- it decodes no tf, reads no plen and adds nothing.  The touched
-// docs pass in doc order, and a doc reaches the running top-k (EventFilter;
-// the event slot for k > kMaxK) only when it holds every MUST slot, no
-// MUST_NOT slot and at least need_should SHOULD slots; a dropped doc's lane is
-// not valid to the filter and leaves its state alone.
-//
-// Which lists start windows.  With a MUST term, the lead slot alone: a matching
-// doc is one of its postings.  Without one, or_kernel's MaxScore rule over the
-// SHOULD slots with the same margin: theta is the k-th best of the matching
-// docs this item has passed to the filter, the reference heap at that doc has
-// seen those docs and more, and a doc that holds only non-essential slots
-// scores at most their summed bound, which is below theta -- it is never an
-// insertion, whether or not it matches.  MUST_NOT slots carry no bound and are
-// never essential; they are read inside the windows the others start.
-struct BoolLds {
-  double acc[kOrWindow];
-  uint32_t bits[kOrWindow / 32];
-  uint32_t held[kOrWindow / 2];   // 16 bits per doc (two docs per word): bit t = slot t's list holds it
-  double norm[256];
-  Event evs[64];
-  uint32_t cur[kMaxOrTerms];      // per term slot: first block of its list not wholly consumed
-  uint32_t cached[kMaxOrTerms];   // ... the block decoded in its cache row (kNoBlock: none)
-};
-static_assert(kMaxOrTerms <= 16, "bool_kernel: a doc's held record is 16 bits");
-
-__global__ __launch_bounds__(64) void bool_kernel(IndexArgs ix, const OrQuery* __restrict__ oqs,
-                                                  const BoolRoles* __restrict__ roles,
-                                                  const OrItem* __restrict__ items, uint32_t n_items,
-                                                  Event* __restrict__ events, uint32_t* __restrict__ ev_cnt,
-                                                  uint32_t* __restrict__ counters,
-                                                  unsigned long long* __restrict__ stats) {
-  __shared__ BoolLds S;
-  // per term slot the current block of its list, decoded: 128 doc ids, 128 tfs
-  extern __shared__ uint32_t or_cache[];
-  const uint32_t l = threadIdx.x & 63;
-  const uint32_t it = blockIdx.x;
-  if (it >= n_items) return;
-  const OrItem I = items[it];
-  const OrQuery* Q = oqs + I.oq;
-  const BoolRoles R = roles[I.oq];
-  const uint32_t nt = uni(static_cast<uint32_t>(Q->nt));
-  const uint32_t k = uni(static_cast<uint32_t>(Q->k));
-  const uint32_t must = uni(R.must_mask), should = uni(R.should_mask), nots = uni(R.not_mask);
-  const uint32_t need = uni(R.need_should);
-  const bool led = must != 0u;   // the lead slot alone starts windows
-  const bool wide = k > static_cast<uint32_t>(kMaxK);   // every matching doc is an event
-  const uint32_t dhi = uni(I.doc_hi), ev_cap = uni(I.ev_cap);
-  Event* ev_out = events + I.ev_base;
-#pragma unroll
-  for (uint32_t i = 0; i < 4; ++i) S.norm[l + 64 * i] = ix.cache[l + 64 * i];
-  for (uint32_t i = l; i < kOrWindow; i += 64) S.acc[i] = 0.0;
-  for (uint32_t i = l; i < kOrWindow / 2; i += 64) S.held[i] = 0u;
-  S.bits[l] = 0u;
-  if (l < static_cast<uint32_t>(kMaxOrTerms)) {
-    S.cur[l] = 0u;
-    S.cached[l] = kNoBlock;
-  }
-  const double ubsum = l < nt ? Q->ubsum[l] : 0.0;
-  uint32_t ess = led ? 1u << uni(static_cast<uint32_t>(R.lead)) : should;   // the slots that start windows
-  __builtin_amdgcn_wave_barrier();
-
-  // block c of list L decoded in slot t's cache row (its tfs too: with_tf); its posting count
-  auto load_block = [&](uint32_t t, const ListDev& L, uint32_t c, bool with_tf) __attribute__((always_inline)) {
-    const uint32_t cnt = c == L.nblk - 1 ? L.tail_cnt : 128u;
-    if (uni(S.cached[t]) == c) return cnt;
-    uint32_t* d = or_cache + t * 256u;
-    __builtin_amdgcn_wave_barrier();
-    if (c == L.nblk - 1 && L.tail != kNoTail) {   // a VInts last block, decoded at load
-      const uint32_t* tp = ix.tails + L.tail;
-      d[l] = l < cnt ? tp[l] : 0u;
-      d[l + 64] = l + 64 < cnt ? tp[l + 64] : 0u;
-      if (with_tf) {
-        d[128 + l] = l < cnt ? tp[cnt + l] : 0u;
-        d[192 + l] = l + 64 < cnt ? tp[cnt + l + 64] : 0u;
-      }
-    } else {
-      const BlockDev bd = ix.blocks[L.blk0 + c];
-      const uint32_t m = uni(ix.blk_meta[L.blk0 + c]);
-      decode_block<true>(ix.blob + L.base + uni(bd.doc_rel), m & 0xFF, cnt, true, uni(bd.prev), d);
-      if (with_tf) decode_block<true>(ix.blob + L.base + uni(bd.tf_rel), m >> 8, cnt, false, 0u, d + 128);
-    }
-    if (l == 0) S.cached[t] = c;
-    __builtin_amdgcn_wave_barrier();
-    return cnt;
-  };
-  // slot t's cursor moved to the first block with a doc >= x
-  auto advance = [&](uint32_t t, const ListDev& L, uint32_t x) __attribute__((always_inline)) {
-    const uint32_t c = uni(find_block(ix.blk_last + L.blk0, uni(S.cur[t]), L.nblk, x));
-    __builtin_amdgcn_wave_barrier();
-    if (l == 0) S.cur[t] = c;
-    __builtin_amdgcn_wave_barrier();
-    return c;
-  };
-
-  EventFilter F;
-  F.k = k;
-  uint32_t ev_n = 0, evb = 0;
-  bool over = false;
-  uint32_t n_win = 0, n_skip = 0, n_touch = 0;
-  auto flush = [&]() __attribute__((always_inline)) {
-    __builtin_amdgcn_wave_barrier();
-    if (ev_n <= ev_cap) {
-      if (l < evb) ev_out[ev_n - evb + l] = S.evs[l];
-    } else {
-      over = true;
-    }
-    __builtin_amdgcn_wave_barrier();
-    evb = 0;
-  };
-  auto emit = [&](double sv, int32_t dv) __attribute__((always_inline)) {
-    if (evb == 64u) flush();
-    if (l == 0) {
-      Event e;
-      e.score = sv;
-      e.doc = dv;
-      e.pad = 0;
-      S.evs[evb] = e;
-    }
-    ++ev_n;
-    ++evb;
-  };
-
-  uint32_t pos = uni(I.doc_lo);   // docs below pos are consumed
-  while (pos < dhi) {
-    // the smallest unconsumed doc id over the window-starting lists
-    uint32_t next = dhi;
-    uint32_t ne_end = 0;   // (statistics) one past the last doc of the non-essential SHOULD lists still open
-    for (uint32_t t = 0; t < nt; ++t) {
-      const ListDev L = ix.lists[Q->list[t]];
-      const uint32_t c = advance(t, L, pos);
-      if (c >= L.nblk) continue;
-      if (!((ess >> t) & 1u)) {
-        if (!led && ((should >> t) & 1u)) ne_end = umax(ne_end, L.last + 1u);
-        continue;
-      }
-      if (uni(ix.blocks[L.blk0 + c].prev) >= next) continue;   // its docs lie past `next`
-      const uint32_t cnt = load_block(t, L, c, true);
-      const uint32_t* d = or_cache + t * 256u;
-      // (the block's last doc is >= pos: the count of docs below pos is < cnt)
-      const uint32_t below = __popcll(__ballot(l < cnt && d[l] < pos)) +
-                             __popcll(__ballot(l + 64 < cnt && d[l + 64] < pos));
-      const uint32_t first = uni(d[below < cnt ? below : cnt - 1]);
-      next = first < next ? first : next;
-    }
-    next = umax(next, pos);   // (every window ends past pos)
-    const uint32_t wb = next & ~(kOrWindow - 1u);
-    const uint32_t lo = umax(wb, pos);
-    {
-      // windows jumped over while a non-essential SHOULD list still had postings
-      const uint32_t to = next >= dhi ? dhi : lo;
-      const uint32_t end = to < ne_end ? to : ne_end;
-      if (end > pos) n_skip += (end - pos + kOrWindow - 1u) / kOrWindow;
-    }
-    if (next >= dhi) break;
-    const uint32_t hi = dhi - wb > kOrWindow ? wb + kOrWindow : dhi;
-    ++n_win;
-    for (uint32_t t = 0; t < nt; ++t) {
-      const ListDev L = ix.lists[Q->list[t]];
-      uint32_t c = advance(t, L, lo);
-      const double idf = L.idf;
-      const bool excl = (nots >> t) & 1u;   // a MUST_NOT slot: membership alone
-      const uint32_t tbit = 1u << t;
-      while (c < L.nblk) {
-        if (uni(ix.blocks[L.blk0 + c].prev) >= hi) break;   // the block starts past the window
-        const uint32_t cnt = load_block(t, L, c, !excl);
-        const uint32_t* d = or_cache + t * 256u;
-        const uint8_t* pl = ix.plen + static_cast<uint64_t>(L.blk0 + c) * 128u;
-#pragma unroll
-        for (uint32_t j = l; j < 128u; j += 64u) {
-          const uint32_t doc = d[j];
-          if (j < cnt && doc >= lo && doc < hi) {
-            const uint32_t i = doc - wb;
-            if (!excl) S.acc[i] = S.acc[i] + bm25_term(idf, d[128 + j], S.norm[pl[j]]);
-            // (two docs share a word of held: the lanes of one term may meet there)
-            atomicOr(&S.held[i >> 1], tbit << (16u * (i & 1u)));
-            atomicOr(&S.bits[i >> 5], 1u << (i & 31u));
-          }
-        }
-        if (uni(ix.blk_last[L.blk0 + c]) >= hi) break;   // it goes on in the next window
-        ++c;
-      }
-      __builtin_amdgcn_wave_barrier();
-      if (l == 0) S.cur[t] = c;
-      __builtin_amdgcn_wave_barrier();   // (and the next term's adds come after this term's)
-    }
-    // the touched docs, in doc order: chunk ch = docs wb + 64 * ch + lane
-    const uint32_t w = S.bits[l];
-    uint64_t nz = __ballot(w != 0u);
-    while (nz) {
-      const uint32_t ch = static_cast<uint32_t>(__builtin_ctzll(nz)) >> 1;
-      nz &= ~(3ull << (2u * ch));
-      // (readlane returns an int: through uint32_t, or the low word's bit 31 would sign-extend)
-      const uint32_t m_lo = static_cast<uint32_t>(__builtin_amdgcn_readlane(w, static_cast<int>(2u * ch)));
-      const uint32_t m_hi = static_cast<uint32_t>(__builtin_amdgcn_readlane(w, static_cast<int>(2u * ch + 1u)));
-      const uint64_t m = (static_cast<uint64_t>(m_hi) << 32) | m_lo;
-      const bool touched = (m >> l) & 1ull;
-      const uint32_t i = 64u * ch + l;
-      const double sc = S.acc[i];
-      const uint32_t h = (S.held[i >> 1] >> (16u * (i & 1u))) & 0xFFFFu;
-      const int32_t doc = static_cast<int32_t>(wb + i);
-      n_touch += __popcll(m);
-      const bool match = touched && (h & must) == must && (h & nots) == 0u &&
-                         static_cast<uint32_t>(__popc(h & should)) >= need;
-      __builtin_amdgcn_wave_barrier();   // (every lane has read its half of a held word)
-      if (l < 32u) S.held[32u * ch + l] = 0u;
-      if (touched) S.acc[i] = 0.0;
-      if (wide) {
-        const uint64_t mm = __ballot(match);
-        const uint32_t n = __popcll(mm);
-        if (ev_n + n <= ev_cap) {
-          if (match) {
-            Event e;
-            e.score = sc;
-            e.doc = doc;
-            e.pad = 0;
-            ev_out[ev_n + __popcll(mm & lanemask_lt())] = e;
-          }
-        } else {
-          over = true;
-        }
-        ev_n += n;
-      } else {
-        F.step(sc, doc, match, emit);
-      }
-    }
-    S.bits[l] = 0u;
-    __builtin_amdgcn_wave_barrier();
-    pos = hi;
-    if (!led && !wide && F.pt_n >= k) {
-      const double thr = readlane_f64(F.pt, static_cast<int>(k) - 1) * kOrMargin;
-      ess = static_cast<uint32_t>(__ballot(l < nt && !(ubsum <= thr))) & should;
-    }
-  }
-  if (evb) flush();
-  if (l == 0) {
-    ev_cnt[it] = over ? 0u : ev_n;
-    if (over) atomicOr(&counters[kCtrError], static_cast<uint32_t>(kErrCapacity));
-    atomicAdd(&stats[kOrStatItems], 1ull);
-    atomicAdd(&stats[kOrStatWindows], static_cast<unsigned long long>(n_win));
-    atomicAdd(&stats[kOrStatSkipped], static_cast<unsigned long long>(n_skip));
-    atomicAdd(&stats[kOrStatTouched], static_cast<unsigned long long>(n_touch));
-    atomicAdd(&stats[kOrStatEvents], static_cast<unsigned long long>(ev_n));
   }
 }
 
@@ -4082,20 +3930,7 @@ __global__ __launch_bounds__(64) void score_docs_kernel(IndexArgs ix, const Scor
       const uint32_t x = static_cast<uint32_t>(__builtin_amdgcn_readlane(doc, __builtin_ctzll(open)));
       cur = uni(find_block(ix.blk_last + L.blk0, cur, L.nblk, x));
       if (cur >= L.nblk) break;   // the list ends below every open doc
-      const uint32_t cnt = cur == L.nblk - 1 ? L.tail_cnt : 128u;
-      if (cur == L.nblk - 1 && L.tail != kNoTail) {   // a VInts last block, decoded at load
-        const uint32_t* tp = ix.tails + L.tail;
-        S.blk[l] = l < cnt ? tp[l] : 0u;
-        S.blk[l + 64] = l + 64 < cnt ? tp[l + 64] : 0u;
-        S.blk[128 + l] = l < cnt ? tp[cnt + l] : 0u;
-        S.blk[192 + l] = l + 64 < cnt ? tp[cnt + l + 64] : 0u;
-        __builtin_amdgcn_wave_barrier();
-      } else {
-        const BlockDev bd = ix.blocks[L.blk0 + cur];
-        const uint32_t m = uni(ix.blk_meta[L.blk0 + cur]);
-        decode_block<true>(ix.blob + L.base + uni(bd.doc_rel), m & 0xFF, cnt, true, uni(bd.prev), S.blk);
-        decode_block<true>(ix.blob + L.base + uni(bd.tf_rel), m >> 8, cnt, false, 0u, S.blk + 128);
-      }
+      const uint32_t cnt = load_list_block(ix, L, cur, true, S.blk);
       const uint32_t last = uni(ix.blk_last[L.blk0 + cur]);
       const bool mine = ((open >> l) & 1ull) && doc <= last;
       if (mine) {

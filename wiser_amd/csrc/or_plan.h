@@ -25,7 +25,26 @@ inline uint32_t blocks_overlapping(const ImageView& v, const ListDev& L, uint32_
   return f < L.nblk ? std::min(first_block(hi - 1), L.nblk - 1) - f + 1 : 0u;
 }
 
-// The plan of one disjunctive query (its resolved terms in oq->list): the
+// The MaxScore bounds of the query's scoring slots (bit t of `scoring`), summed
+// in ascending (bound, slot) order into oq->ubsum; 0.0 for the other slots.
+inline void sum_maxscore_bounds(const ImageView& v, uint32_t scoring, OrQuery* oq) {
+  int by[kMaxOrTerms];
+  int ns = 0;
+  for (int t = 0; t < oq->nt; ++t) {
+    oq->ubsum[t] = 0.0;
+    if ((scoring >> t) & 1u) by[ns++] = t;
+  }
+  auto ub = [&](int t) { return 2.2 * v.lists[oq->list[t]].idf; };
+  std::stable_sort(by, by + ns, [&](int a, int c) { return ub(a) < ub(c); });
+  double sum = 0.0;
+  for (int r = 0; r < ns; ++r) {
+    sum += ub(by[r]);
+    oq->ubsum[by[r]] = sum;
+  }
+}
+
+// The plan of one disjunctive query (its resolved terms in oq->list; bit t of
+// `scoring`: slot t carries a MaxScore bound, sum_maxscore_bounds): the
 // image's doc range cut into items at the last doc of every s-th block of the
 // query's longest list, s chosen so that an item carries about `target` blocks
 // over all its lists (doc ids spread alike over the lists' blocks), and each
@@ -33,18 +52,9 @@ inline uint32_t blocks_overlapping(const ImageView& v, const ListDev& L, uint32_
 // event, or every posting of the blocks that overlap it.  Appends the items
 // and advances *ev_total.
 inline void plan_or_query(const ImageView& v, uint32_t target, OrQuery* oq, std::vector<OrItem>* items,
-                          uint64_t* ev_total) {
+                          uint64_t* ev_total, uint32_t scoring = ~0u) {
   const int nt = oq->nt;
-  // MaxScore bounds, summed in ascending (bound, slot) order
-  int by[kMaxOrTerms];
-  for (int t = 0; t < nt; ++t) by[t] = t;
-  auto ub = [&](int t) { return 2.2 * v.lists[oq->list[t]].idf; };
-  std::stable_sort(by, by + nt, [&](int a, int c) { return ub(a) < ub(c); });
-  double sum = 0.0;
-  for (int r = 0; r < nt; ++r) {
-    sum += ub(by[r]);
-    oq->ubsum[by[r]] = sum;
-  }
+  sum_maxscore_bounds(v, scoring, oq);
   uint64_t total = 0;
   int lg = 0;
   uint32_t top = 0;   // one past the last doc of its lists in the image

@@ -26,14 +26,7 @@ extern "C" int wsr_score_docs(wsr_handle* h, const wsr_query* q, int32_t nq, con
     std::memset(out, 0, sizeof(wsr_doc_score) * total);
     return WSR_OK;
   }
-  std::unique_ptr<ScoreCtx> c;
-  {
-    std::lock_guard<std::mutex> g(h->score_mu);
-    if (!h->score_pool.empty()) {
-      c = std::move(h->score_pool.back());
-      h->score_pool.pop_back();
-    }
-  }
+  std::unique_ptr<ScoreCtx> c = h->score_pool.take();
   try {
     HIP_OK(hipSetDevice(h->device));
     if (!c) {
@@ -59,7 +52,6 @@ extern "C" int wsr_score_docs(wsr_handle* h, const wsr_query* q, int32_t nq, con
     if (c && c->st) (void)hipStreamSynchronize(c->st);
     return fail(WSR_E_HIP, e.what());
   }
-  std::lock_guard<std::mutex> g(h->score_mu);
-  if (h->score_pool.size() < 8) h->score_pool.push_back(std::move(c));
+  h->score_pool.give(std::move(c));
   return WSR_OK;
 }
