@@ -9,7 +9,7 @@ ORACLE  := oracle/_build/liboracle.so
 SRCS    := wiser_amd/csrc/writer.cc wiser_amd/csrc/index.cc wiser_amd/csrc/engine.cc \
            wiser_amd/csrc/shard_exchange.cc wiser_amd/csrc/batch_plan.cc wiser_amd/csrc/server.cc \
            wiser_amd/csrc/score_plan.cc wiser_amd/csrc/score_docs.cc \
-           wiser_amd/csrc/bool_plan.cc wiser_amd/csrc/bool_search.cc \
+           wiser_amd/csrc/bool_plan.cc wiser_amd/csrc/bool_search.cc wiser_amd/csrc/count_bool.cc \
            wiser_amd/csrc/docstore.cc \
            wiser_amd/csrc/snippet.cc wiser_amd/csrc/kernels.hip
 HDRS    := $(wildcard wiser_amd/csrc/*.h) include/wiser_hip.h
@@ -32,6 +32,8 @@ SCLI    := wiser_amd/_lib/score_cli
 BLMIMG  := wiser_amd/_lib/bloom_image_check
 BOPLAN  := wiser_amd/_lib/bool_plan_check
 BOCLI   := wiser_amd/_lib/bool_cli
+COPLAN  := wiser_amd/_lib/count_plan_check
+COCLI   := wiser_amd/_lib/count_cli
 
 # (the buffer owner's, the two plans' and the shard layout's checks are tests of those files
 # alone: a tree whose tests/ does not hold their sources still builds everything else)
@@ -42,7 +44,9 @@ all: $(LIB) $(ORACLE) $(CLI) $(CALIB) $(DICT) $(if $(wildcard tests/cpp/dev_mem_
      $(if $(wildcard tests/cpp/score_cli.cc),$(SCLI)) \
      $(if $(wildcard tests/cpp/bloom_image_check.cc),$(BLMIMG)) \
      $(if $(wildcard tests/cpp/bool_plan_check.cc),$(BOPLAN)) \
-     $(if $(wildcard tests/cpp/bool_cli.cc),$(BOCLI))
+     $(if $(wildcard tests/cpp/bool_cli.cc),$(BOCLI)) \
+     $(if $(wildcard tests/cpp/count_plan_check.cc),$(COPLAN)) \
+     $(if $(wildcard tests/cpp/count_cli.cc),$(COCLI))
 
 # CPU check of the term dictionary (tests/test_dictionary.py)
 $(DICT): tests/cpp/dict_check.cc wiser_amd/csrc/index.h $(LIB)
@@ -82,6 +86,12 @@ $(BOPLAN): tests/cpp/bool_plan_check.cc wiser_amd/csrc/bool_plan.cc wiser_amd/cs
 	@mkdir -p wiser_amd/_lib
 	$(CXX) -O2 -std=c++17 -Wall -o $@ tests/cpp/bool_plan_check.cc wiser_amd/csrc/bool_plan.cc
 
+# CPU check of the wsr_count_bool plan on a hand-made image (tests/test_count_plan.py): no HIP, no engine
+$(COPLAN): tests/cpp/count_plan_check.cc wiser_amd/csrc/bool_plan.cc wiser_amd/csrc/bool_plan.h \
+           wiser_amd/csrc/or_plan.h wiser_amd/csrc/batch_plan.h wiser_amd/csrc/engine_types.h include/wiser_hip.h
+	@mkdir -p wiser_amd/_lib
+	$(CXX) -O2 -std=c++17 -Wall -o $@ tests/cpp/count_plan_check.cc wiser_amd/csrc/bool_plan.cc
+
 # counter calibration (profiles only): known-byte reads for rocprofv3 --pmc
 $(CALIB): scripts/calib_ea.hip
 	@mkdir -p wiser_amd/_lib
@@ -97,6 +107,10 @@ $(SCLI): tests/cpp/score_cli.cc include/wiser_hip_engine.hpp include/wiser_hip.h
 # C++ host of the boolean query mirror (tests/test_gpu_bool.py)
 $(BOCLI): tests/cpp/bool_cli.cc include/wiser_hip_engine.hpp include/wiser_hip.h $(LIB)
 	$(CXX) -O2 -std=c++17 -Iinclude -o $@ tests/cpp/bool_cli.cc -Lwiser_amd/_lib -lwiser_hip -Wl,-rpath,'$$ORIGIN'
+
+# C++ host of the match-count mirror (tests/test_gpu_count.py)
+$(COCLI): tests/cpp/count_cli.cc include/wiser_hip_engine.hpp include/wiser_hip.h $(LIB)
+	$(CXX) -O2 -std=c++17 -Iinclude -o $@ tests/cpp/count_cli.cc -Lwiser_amd/_lib -lwiser_hip -Wl,-rpath,'$$ORIGIN'
 
 $(OBJDIR)/%.o: wiser_amd/csrc/% $(HDRS)
 	@mkdir -p $(OBJDIR)

@@ -309,6 +309,46 @@ struct wsr_or_stats;
 int wsr_search_bool_ex(wsr_handle* h, const wsr_bool_query* q, int32_t nq, int32_t hit_stride,
                        wsr_hit* hits, int32_t* n_hits, int32_t item_blocks, struct wsr_or_stats* stats);
 
+/* Exact match counts of boolean queries (beyond the reference): how many docs
+ * match, where every ranking entry point answers which k rank best -- the
+ * figure beside a result page, for pagination, for asking whether a filter is
+ * selective.  No ranking path can give it: k stops at WSR_MAX_K and each of
+ * them prunes docs before it scores them.
+ *
+ * Result.  counts[i] is the number of docs of the image's doc range that match
+ * query i under the Match rule of wsr_search_bool, word for word: every MUST
+ * term's list holds the doc, no MUST_NOT term's list holds it, and
+ * S(d) >= max(min_should, 1 if the query has no MUST term else 0); a term
+ * given twice is two slots; missing terms (list id -1) behave as they do
+ * there.
+ * k is ignored entirely: zero, negative values and values above WSR_MAX_K are
+ * accepted and change nothing (as wsr_score_docs ignores k).
+ * A count of 0 is a result, not an error: a missing MUST term, min_should
+ * above the number of resolvable SHOULD slots, a query of MUST_NOT terms
+ * only, n_terms = 0.
+ * Identities: one MUST term, or one SHOULD term, on an unsharded engine counts
+ * wsr_lookup's doc_freq; the count is at least wsr_search_bool's n_hits at any
+ * k, and equal to it whenever the count is at most k.
+ * Errors, all checked on the host before anything is enqueued (a refused call
+ * writes nothing to counts): n_terms > WSR_MAX_OR_TERMS is WSR_E_LIMIT; a role
+ * outside 0..2, min_should < 0, n_terms < 0, a list id below -1 or past the
+ * index, nq < 0 and null arguments with nq > 0 are WSR_E_INVALID.
+ * Calling.  counts: nq entries.  Synchronous; may be called concurrently on
+ * one handle; nq = 0 is fine.  On a doc-range shard engine the count covers
+ * the image's doc range: each doc lives in one shard, so the shards of a
+ * partition add up to the whole-index count and a caller with W shards sums W
+ * answers (no shard step is needed).  Counting takes no part in the
+ * micro-batching server or the text log format, and has no phrase clauses. */
+int wsr_count_bool(wsr_handle* h, const wsr_bool_query* q, int32_t nq, int64_t* counts);
+/* wsr_count_bool with wsr_search_bool_ex's two knobs: item_blocks as there;
+ * stats, when not NULL, receives the call's counters in wsr_or_stats' terms:
+ * items and windows run, touched_docs = the docs of those windows held by at
+ * least one kept term slot (MUST_NOT slots included); windows_skipped and
+ * events are always 0 (nothing is skipped on a threshold, nothing is replayed).
+ * All 0 when no query of the call reached the device. */
+int wsr_count_bool_ex(wsr_handle* h, const wsr_bool_query* q, int32_t nq, int64_t* counts,
+                      int32_t item_blocks, struct wsr_or_stats* stats);
+
 /* Queries as text, the reference's query-log format (QueryProducerByLog,
  * query_pool.h:319-378): one query per line, terms separated by spaces, a
  * line in double quotes is a phrase query.  Every term is resolved through the

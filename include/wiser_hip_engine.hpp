@@ -189,6 +189,30 @@ class VacuumHipEngine {
     return out;
   }
 
+  // wsr_count_bool: how many docs match each query under SearchBool's match
+  // rule.  n_results is ignored; a term missing from the index is list id -1.
+  // On a doc-range shard engine: the matches in the shard's doc range.
+  std::vector<int64_t> CountBool(const std::vector<BoolQuery>& qs) {
+    std::vector<wsr_bool_query> in(qs.size());
+    for (size_t i = 0; i < qs.size(); ++i) {
+      const BoolQuery& q = qs[i];
+      if (q.terms.size() > WSR_MAX_OR_TERMS)
+        throw std::runtime_error("wiser_hip: more than WSR_MAX_OR_TERMS terms in a boolean query");
+      wsr_bool_query& w = in[i];
+      w = wsr_bool_query{};
+      w.n_terms = static_cast<int32_t>(q.terms.size());
+      w.min_should = q.min_should;
+      for (size_t t = 0; t < q.terms.size(); ++t) {
+        int32_t df;
+        check(wsr_lookup(h_, q.terms[t].first.c_str(), &w.list_ids[t], &df));
+        w.role[t] = static_cast<uint8_t>(q.terms[t].second);
+      }
+    }
+    std::vector<int64_t> counts(qs.size());
+    check(wsr_count_bool(h_, in.data(), static_cast<int32_t>(qs.size()), counts.data()));
+    return counts;
+  }
+
   std::vector<SearchResult> SearchBatch(const std::vector<SearchQuery>& qs) {
     std::vector<wsr_query> in(qs.size());
     std::vector<std::vector<int32_t>> more(qs.size());   // terms past WSR_MAX_TERMS

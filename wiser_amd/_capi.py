@@ -143,6 +143,9 @@ _sigs = {
     "wsr_check_bool_query": (C.c_int, [_P, C.POINTER(BoolQuery)]),
     "wsr_search_bool_ex": (C.c_int, [_P, C.POINTER(BoolQuery), C.c_int32, C.c_int32, C.POINTER(Hit),
                                      C.POINTER(C.c_int32), C.c_int32, C.POINTER(OrStats)]),
+    "wsr_count_bool": (C.c_int, [_P, C.POINTER(BoolQuery), C.c_int32, C.POINTER(C.c_int64)]),
+    "wsr_count_bool_ex": (C.c_int, [_P, C.POINTER(BoolQuery), C.c_int32, C.POINTER(C.c_int64), C.c_int32,
+                                    C.POINTER(OrStats)]),
     "wsr_resolve_text": (C.c_int, [_P, C.c_char_p, C.c_int64, C.c_int32, C.c_int32, C.POINTER(Query),
                                    C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64]),
     "wsr_search_text": (C.c_int, [_P, C.c_char_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,

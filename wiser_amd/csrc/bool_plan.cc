@@ -1,4 +1,4 @@
-// The host's plan of a wsr_search_bool call (bool_plan.h).
+// The host's plan of a wsr_search_bool or wsr_count_bool call (bool_plan.h).
 #include "bool_plan.h"
 
 #include <algorithm>
@@ -12,11 +12,11 @@ int fail(std::string* err, int code, const std::string& msg) {
   *err = msg;
   return code;
 }
-}  // namespace
 
-int check_bool_query(const ImageView& v, const wsr_bool_query& q, std::string* err) {
+// check_bool_query's rule; counting: k is not looked at (wsr_count_bool)
+int check_query(const ImageView& v, const wsr_bool_query& q, bool counting, std::string* err) {
   if (q.n_terms > WSR_MAX_OR_TERMS) return fail(err, WSR_E_LIMIT, "a boolean query has at most WSR_MAX_OR_TERMS terms");
-  if (q.k > WSR_MAX_K) return fail(err, WSR_E_LIMIT, "k over WSR_MAX_K");
+  if (!counting && q.k > WSR_MAX_K) return fail(err, WSR_E_LIMIT, "k over WSR_MAX_K");
   if (q.n_terms < 0) return fail(err, WSR_E_INVALID, "n_terms is negative");
   if (q.min_should < 0) return fail(err, WSR_E_INVALID, "min_should is negative");
   const int32_t n_lists = static_cast<int32_t>(v.n_lists);
@@ -27,8 +27,9 @@ int check_bool_query(const ImageView& v, const wsr_bool_query& q, std::string* e
   return WSR_OK;
 }
 
-int plan_bool(const ImageView& v, const wsr_bool_query* q, int32_t nq, int32_t stride, bool have_out,
-              uint32_t target, BoolPlan* out, std::string* err) {
+// plan_bool, or (counting) plan_count: no k anywhere and no event slots
+int plan(const ImageView& v, const wsr_bool_query* q, int32_t nq, int32_t stride, bool have_out, uint32_t target,
+         bool counting, BoolPlan* out, std::string* err) {
   BoolPlan& p = *out;
   p.qs.clear();
   p.roles.clear();
@@ -39,18 +40,18 @@ int plan_bool(const ImageView& v, const wsr_bool_query* q, int32_t nq, int32_t s
   if (nq < 0 || (nq > 0 && (!q || !have_out))) return fail(err, WSR_E_INVALID, "bad arguments");
   for (int i = 0; i < nq; ++i) {
     auto at = [i] { return "query " + std::to_string(i) + ": "; };
-    if (q[i].k > stride) return fail(err, WSR_E_LIMIT, at() + "k over the call's hit stride");
+    if (!counting && q[i].k > stride) return fail(err, WSR_E_LIMIT, at() + "k over the call's hit stride");
     std::string why;
-    const int rc = check_bool_query(v, q[i], &why);
+    const int rc = check_query(v, q[i], counting, &why);
     if (rc) return fail(err, rc, at() + why);
   }
   for (int i = 0; i < nq; ++i) {
     const wsr_bool_query& s = q[i];
-    if (s.k <= 0 || s.n_terms == 0) continue;
+    if ((!counting && s.k <= 0) || s.n_terms == 0) continue;
     OrQuery oq{};
     BoolRoles r{};
     oq.q = i;
-    oq.k = s.k;
+    oq.k = counting ? 0 : s.k;
     bool has_must = false, settled = false;
     for (int t = 0; t < s.n_terms; ++t) {
       const int32_t id = s.list_ids[t];
@@ -97,11 +98,30 @@ int plan_bool(const ImageView& v, const wsr_bool_query* q, int32_t nq, int32_t s
     if (!oq.n_items) continue;
     for (uint32_t j = 0; j < oq.n_items; ++j) p.items[oq.item_base + j].oq = static_cast<uint32_t>(p.qs.size());
     p.nt_max = std::max(p.nt_max, oq.nt);
-    (oq.k > kMaxK ? p.wide : p.narrow) = true;
+    if (!counting) (oq.k > kMaxK ? p.wide : p.narrow) = true;
     p.qs.push_back(oq);
     p.roles.push_back(r);
   }
+  if (counting) {
+    for (OrItem& it : p.items) it.ev_cap = 0, it.ev_base = 0;
+    p.ev_total = 0;
+  }
   return WSR_OK;
+}
+}  // namespace
+
+int check_bool_query(const ImageView& v, const wsr_bool_query& q, std::string* err) {
+  return check_query(v, q, false, err);
+}
+
+int plan_bool(const ImageView& v, const wsr_bool_query* q, int32_t nq, int32_t stride, bool have_out,
+              uint32_t target, BoolPlan* out, std::string* err) {
+  return plan(v, q, nq, stride, have_out, target, false, out, err);
+}
+
+int plan_count(const ImageView& v, const wsr_bool_query* q, int32_t nq, bool have_out, uint32_t target,
+               BoolPlan* out, std::string* err) {
+  return plan(v, q, nq, 0, have_out, target, true, out, err);
 }
 
 }  // namespace wiser

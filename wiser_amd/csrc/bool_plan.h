@@ -48,4 +48,12 @@ int check_bool_query(const ImageView& v, const wsr_bool_query& q, std::string* e
 int plan_bool(const ImageView& v, const wsr_bool_query* q, int32_t nq, int32_t stride, bool have_out,
               uint32_t target, BoolPlan* out, std::string* err);
 
+// The plan of a wsr_count_bool call: plan_bool's checks, kept slots, roles,
+// lead and items (the same doc ranges, the items without a lead block
+// dropped), without k: k is neither checked nor read (no "k <= 0 is settled",
+// OrQuery::k is 0, narrow and wide stay false) and no event slot is sized
+// (every ev_cap and ev_base, and ev_total, are 0).  have_out: counts is given.
+int plan_count(const ImageView& v, const wsr_bool_query* q, int32_t nq, bool have_out, uint32_t target,
+               BoolPlan* out, std::string* err);
+
 }  // namespace wiser

@@ -98,6 +98,18 @@ struct BoolCtx {
   gpu::DevBuf<int32_t> d_nhits;
 };
 
+// What one wsr_count_bool call holds on the device (count_bool.cc): kept in a
+// per-handle pool, one per concurrent caller, as the BoolCtx.
+struct CountCtx {
+  gpu::Stream st;
+  gpu::DevBuf<wiser::OrQuery> d_qs;
+  gpu::DevBuf<wiser::BoolRoles> d_roles;     // (sized together with d_qs)
+  gpu::DevBuf<wiser::OrItem> d_items;
+  gpu::DevBuf<uint32_t> d_icnt;              // matching docs per item (sized together with d_items)
+  gpu::DevBuf<uint32_t> d_ctr;               // kNumCounters (the error flags)
+  gpu::DevBuf<unsigned long long> d_stats;   // kNumOrStats
+};
+
 struct wsr_handle {
   std::mutex mu;
   int device = 0;
@@ -146,6 +158,7 @@ struct wsr_handle {
   int gen_cap = 0;     // general workgroups launched at most
   CtxPool<ScoreCtx> score_pool;         // wsr_score_docs' reusable contexts
   CtxPool<BoolCtx> bool_pool;           // wsr_search_bool's
+  CtxPool<CountCtx> count_pool;         // wsr_count_bool's
   // what the upload plan (batch_plan.h) reads of the handle
   wiser::ImageView view() const {
     wiser::ImageView v;

@@ -208,6 +208,17 @@ hipError_t launch_bool_items(const IndexArgs& ix, const OrQuery* oq, const BoolR
                              uint32_t n_items, int nt_max, Event* events, uint32_t* ev_cnt, uint32_t* counters,
                              unsigned long long* stats, hipStream_t st);
 
+// Exact match counts (wsr_count_bool): count_kernel, one wave per item of
+// plan_count's tables (oq[i] and roles[i] as for launch_bool_items; k, ubsum
+// and the items' event slots are not read).  item_count[i] = matching docs of
+// item i's range; every item of the launch is written.  counters: the error
+// flags; stats: kNumOrStats u64 (zeroed by the caller), of which items,
+// windows and touched docs are counted.  nt_max sizes the decoded-block cache
+// in LDS (128 doc ids per slot).
+hipError_t launch_count_items(const IndexArgs& ix, const OrQuery* oq, const BoolRoles* roles, const OrItem* items,
+                              uint32_t n_items, int nt_max, uint32_t* item_count, uint32_t* counters,
+                              unsigned long long* stats, hipStream_t st);
+
 // Given (query, doc) pairs (wsr_score_docs): one wave per item of at most
 // kScoreLanes candidates, sorted by doc id at docs[first ..]; the answer of
 // candidate j goes to out[index[j]].  Rows no item covers are left as they are

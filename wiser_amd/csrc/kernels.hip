@@ -3849,6 +3849,201 @@ __global__ __launch_bounds__(64) void bool_kernel(IndexArgs ix, const OrQuery* _
   window_item<true>(S, or_cache, ix, oqs, roles, items, blockIdx.x, events, ev_cnt, counters, stats);
 }
 
+// ------------------------------------------------ exact match counts --
+// wsr_count_bool: count_kernel, one wave per item of a boolean query (the
+// items, kept slots and roles are plan_bool's; bool_plan.h, plan_count).  It
+// answers how many docs of the item's range match, and nothing else: no tf, no
+// plen, no score, no top-k, no events.  The range is walked in windows of
+// kOrWindow docs aligned to kOrWindow, as window_item walks it, and a doc's
+// whole state is one bit per kept slot: bm[t] is slot t's bitmap of the
+// window, word w of it docs wb + 32 w .. wb + 32 w + 31, one word per lane.
+//
+// Why the count is exact.  (1) Which windows run: with a MUST term a matching
+// doc is a posting of the lead list, without one it is a posting of a SHOULD
+// list (need_should >= 1); the next window is the one that holds the smallest
+// doc id >= pos over those lists, so a window that is jumped over holds no
+// posting of them and no matching doc.  There is no threshold, so nothing else
+// is ever set aside.  (2) Inside a window every kept slot's blocks that
+// overlap [lo, hi) are decoded and every posting in [lo, hi) sets its bit, so
+// after the wave barrier bit i of bm[t] says exactly "slot t's list holds doc
+// wb + i" for the window's docs of the item; bits of docs outside [lo, hi) are
+// never set.  (3) The match rule is evaluated bitwise on 32 docs per lane:
+// mustw = AND of the MUST words, notw = OR of the MUST_NOT words, shouldw =
+// "at least need of the SHOULD words have the bit" (all ones for need = 0,
+// their OR for need = 1, else a bit-sliced count -- five planes hold 0..16,
+// one ripple add per SHOULD word -- compared with need plane by plane), and
+// m = mustw & ~notw & shouldw.  With a MUST slot m lies inside its bits,
+// without one need >= 1 puts it inside the SHOULD bits: m has no bit outside
+// [lo, hi), and popc(m) is the window's matching docs.  (4) Windows of an item
+// are disjoint and the host's items are disjoint, so the sums add up; a lane's
+// counter stays below 2^31 because an item's range does.
+//
+// The loop control is scalar: the slot loops run to the uniform nt, the role
+// tests read uniform masks, cursors go through readfirstlane.
+struct CountLds {
+  uint32_t bm[kMaxOrTerms][kOrWindow / 32];
+  uint32_t cur[kMaxOrTerms];      // per slot: first block of its list not wholly consumed
+  uint32_t cached[kMaxOrTerms];   // ... the block decoded in its cache row (kNoBlock: none)
+};
+static_assert(kOrWindow / 32 == 64, "count_kernel: one bitmap word per lane and slot");
+static_assert(kMaxOrTerms <= 16, "count_kernel: five planes count 0..16 SHOULD slots");
+
+// count_cache: per slot the current block of its list, decoded (128 doc ids)
+__global__ __launch_bounds__(64) void count_kernel(IndexArgs ix, const OrQuery* __restrict__ oqs,
+                                                   const BoolRoles* __restrict__ roles,
+                                                   const OrItem* __restrict__ items, uint32_t n_items,
+                                                   uint32_t* __restrict__ item_count,
+                                                   uint32_t* __restrict__ counters,
+                                                   unsigned long long* __restrict__ stats) {
+  __shared__ CountLds S;
+  extern __shared__ uint32_t count_cache[];
+  const uint32_t it = blockIdx.x;
+  if (it >= n_items) return;
+  const uint32_t l = threadIdx.x & 63;
+  const OrItem I = items[it];
+  const OrQuery* Q = oqs + I.oq;
+  const BoolRoles R = roles[I.oq];
+  const uint32_t nt = uni(static_cast<uint32_t>(Q->nt));
+  const uint32_t dhi = uni(I.doc_hi);
+  const uint32_t must = uni(R.must_mask), should = uni(R.should_mask), nots = uni(R.not_mask);
+  const uint32_t need = umax(uni(R.need_should), must ? 0u : 1u);
+  if (nt > static_cast<uint32_t>(kMaxOrTerms) || need > static_cast<uint32_t>(kMaxOrTerms) ||
+      (must && uni(static_cast<uint32_t>(R.lead)) >= nt)) {   // (no table of the host's)
+    if (l == 0) {
+      item_count[it] = 0u;
+      atomicOr(&counters[kCtrError], static_cast<uint32_t>(kErrLimit));
+    }
+    return;
+  }
+  const uint32_t starts = must ? 1u << uni(static_cast<uint32_t>(R.lead)) : should;   // the slots that start windows
+  for (uint32_t t = 0; t < nt; ++t) S.bm[t][l] = 0u;
+  if (l < static_cast<uint32_t>(kMaxOrTerms)) {
+    S.cur[l] = 0u;
+    S.cached[l] = kNoBlock;
+  }
+  __builtin_amdgcn_wave_barrier();
+
+  // block c of list L decoded in slot t's cache row; its posting count
+  auto load_block = [&](uint32_t t, const ListDev& L, uint32_t c) __attribute__((always_inline)) {
+    const uint32_t cnt = block_count(L, c);
+    if (uni(S.cached[t]) == c) return cnt;
+    __builtin_amdgcn_wave_barrier();
+    load_list_block(ix, L, c, false, count_cache + t * 128u);
+    if (l == 0) S.cached[t] = c;
+    __builtin_amdgcn_wave_barrier();
+    return cnt;
+  };
+  // slot t's cursor moved to the first block with a doc >= x
+  auto advance = [&](uint32_t t, const ListDev& L, uint32_t x) __attribute__((always_inline)) {
+    const uint32_t c = uni(find_block(ix.blk_last + L.blk0, uni(S.cur[t]), L.nblk, x));
+    __builtin_amdgcn_wave_barrier();
+    if (l == 0) S.cur[t] = c;
+    __builtin_amdgcn_wave_barrier();
+    return c;
+  };
+
+  uint32_t n_match = 0, n_touch = 0;   // this lane's words
+  uint32_t n_win = 0;
+  uint32_t pos = uni(I.doc_lo);   // docs below pos are consumed
+  while (pos < dhi) {
+    // the smallest unconsumed doc id over the starting lists
+    uint32_t next = dhi;
+    for (uint32_t t = 0; t < nt; ++t) {
+      if (!((starts >> t) & 1u)) continue;
+      const ListDev L = ix.lists[Q->list[t]];
+      const uint32_t c = advance(t, L, pos);
+      if (c >= L.nblk) continue;
+      if (uni(ix.blocks[L.blk0 + c].prev) >= next) continue;   // its docs lie past `next`
+      const uint32_t cnt = load_block(t, L, c);
+      const uint32_t* d = count_cache + t * 128u;
+      // (the block's last doc is >= pos: the count of docs below pos is < cnt)
+      const uint32_t below = __popcll(__ballot(l < cnt && d[l] < pos)) +
+                             __popcll(__ballot(l + 64 < cnt && d[l + 64] < pos));
+      const uint32_t first = uni(d[below < cnt ? below : cnt - 1]);
+      next = first < next ? first : next;
+    }
+    next = umax(next, pos);   // (every window ends past pos)
+    if (next >= dhi) break;
+    const uint32_t wb = next & ~(kOrWindow - 1u);
+    const uint32_t lo = umax(wb, pos);
+    const uint32_t hi = dhi - wb > kOrWindow ? wb + kOrWindow : dhi;
+    ++n_win;
+    for (uint32_t t = 0; t < nt; ++t) {
+      const ListDev L = ix.lists[Q->list[t]];
+      uint32_t c = advance(t, L, lo);
+      while (c < L.nblk) {
+        if (uni(ix.blocks[L.blk0 + c].prev) >= hi) break;   // the block starts past the window
+        const uint32_t cnt = load_block(t, L, c);
+        const uint32_t* d = count_cache + t * 128u;
+#pragma unroll
+        for (uint32_t j = l; j < 128u; j += 64u) {
+          const uint32_t doc = d[j];
+          if (j < cnt && doc >= lo && doc < hi) {
+            const uint32_t i = doc - wb;
+            // (32 docs share a word: the lanes of one term meet there)
+            atomicOr(&S.bm[t][i >> 5], 1u << (i & 31u));
+          }
+        }
+        if (uni(ix.blk_last[L.blk0 + c]) >= hi) break;   // it goes on in the next window
+        ++c;
+      }
+      __builtin_amdgcn_wave_barrier();
+      if (l == 0) S.cur[t] = c;
+      __builtin_amdgcn_wave_barrier();
+    }
+    // the match rule on this lane's 32 docs; the words it read are cleared for the next window
+    uint32_t mustw = 0xFFFFFFFFu, notw = 0u, orw = 0u, anyw = 0u;
+    uint32_t plane[5] = {0u, 0u, 0u, 0u, 0u};   // bit i of plane[b]: bit b of doc i's SHOULD count
+    for (uint32_t t = 0; t < nt; ++t) {
+      const uint32_t w = S.bm[t][l];
+      S.bm[t][l] = 0u;
+      anyw |= w;
+      if ((must >> t) & 1u) {
+        mustw &= w;
+      } else if ((nots >> t) & 1u) {
+        notw |= w;
+      } else {
+        orw |= w;
+        if (need >= 2u) {
+          uint32_t carry = w;
+#pragma unroll
+          for (uint32_t b = 0; b < 5u; ++b) {
+            const uint32_t up = plane[b] & carry;
+            plane[b] ^= carry;
+            carry = up;
+          }
+        }
+      }
+    }
+    uint32_t shouldw = 0xFFFFFFFFu;
+    if (need == 1u) {
+      shouldw = orw;
+    } else if (need >= 2u) {
+      // count >= need, from the top plane down
+      uint32_t gt = 0u, eq = 0xFFFFFFFFu;
+#pragma unroll
+      for (int b = 4; b >= 0; --b) {
+        const uint32_t nb = ((need >> b) & 1u) ? 0xFFFFFFFFu : 0u;
+        gt |= eq & plane[b] & ~nb;
+        eq &= ~(plane[b] ^ nb);
+      }
+      shouldw = gt | eq;
+    }
+    n_match += __popc(mustw & ~notw & shouldw);
+    n_touch += __popc(anyw);
+    __builtin_amdgcn_wave_barrier();
+    pos = hi;
+  }
+  const uint32_t total = static_cast<uint32_t>(__builtin_amdgcn_readlane(wave_incl_scan(n_match), 63));
+  const uint32_t touched = static_cast<uint32_t>(__builtin_amdgcn_readlane(wave_incl_scan(n_touch), 63));
+  if (l == 0) {
+    item_count[it] = total;
+    atomicAdd(&stats[kOrStatItems], 1ull);
+    atomicAdd(&stats[kOrStatWindows], static_cast<unsigned long long>(n_win));
+    atomicAdd(&stats[kOrStatTouched], static_cast<unsigned long long>(touched));
+  }
+}
+
 // One wave per OR query: the events of its items (doc-id order) through the
 // restated heap (HeapSink, or LdsHeapSink for k > kMaxK), then SortHeap.
 template <bool kWide>
@@ -3977,6 +4172,15 @@ hipError_t launch_bool_items(const IndexArgs& ix, const OrQuery* oq, const BoolR
   if (!n_items) return hipSuccess;
   hipLaunchKernelGGL(bool_kernel, dim3(n_items), dim3(64), sizeof(uint32_t) * 256u * static_cast<uint32_t>(nt_max),
                      st, ix, oq, roles, items, n_items, events, ev_cnt, counters, stats);
+  return hipGetLastError();
+}
+
+hipError_t launch_count_items(const IndexArgs& ix, const OrQuery* oq, const BoolRoles* roles, const OrItem* items,
+                              uint32_t n_items, int nt_max, uint32_t* item_count, uint32_t* counters,
+                              unsigned long long* stats, hipStream_t st) {
+  if (!n_items) return hipSuccess;
+  hipLaunchKernelGGL(count_kernel, dim3(n_items), dim3(64), sizeof(uint32_t) * 128u * static_cast<uint32_t>(nt_max),
+                     st, ix, oq, roles, items, n_items, item_count, counters, stats);
   return hipGetLastError();
 }
 

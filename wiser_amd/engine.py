@@ -296,6 +296,30 @@ class VacuumEngine:
             out.append(r)
         return out
 
+    # ---- exact match counts ---------------------------------------------
+    def count_bool(self, queries: Sequence[BoolQuery]) -> List[int]:
+        """wsr_count_bool: how many docs match each query under search_bool's
+        match rule (n_results is ignored; on a doc-range shard engine, the
+        matches in the shard's doc range -- the shards of a partition add up)."""
+        if not queries:
+            return []
+        n = len(queries)
+        arr = (_capi.BoolQuery * n)(*[self.resolve_bool(bq)[0] for bq in queries])
+        counts = (C.c_int64 * n)()
+        check(lib.wsr_count_bool(self._h, arr, n, counts))
+        return list(counts)
+
+    def count(self, query: SearchQuery) -> int:
+        """How many docs a Search of the query would rank from: the docs that
+        hold every term, or any term with match_any.  Phrase queries and more
+        than MAX_OR_TERMS terms are refused."""
+        if query.is_phrase and len(query.terms) > 1:
+            raise _capi.WiserError(_capi.E_INVALID, "count takes no phrase query")
+        if len(query.terms) > _capi.MAX_OR_TERMS:
+            raise _capi.WiserError(_capi.E_LIMIT, f"more than {_capi.MAX_OR_TERMS} terms in a count query")
+        role = "should" if query.match_any else "must"
+        return self.count_bool([BoolQuery([(t, role) for t in query.terms])])[0]
+
     # ---- given (query, doc) pairs -------------------------------------
     def resolve_terms(self, query: SearchQuery):
         """-> wsr_query for wsr_score_docs: every term looked up (-1: not in the
