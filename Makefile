@@ -10,6 +10,7 @@ SRCS    := wiser_amd/csrc/writer.cc wiser_amd/csrc/index.cc wiser_amd/csrc/engin
            wiser_amd/csrc/shard_exchange.cc wiser_amd/csrc/batch_plan.cc wiser_amd/csrc/server.cc \
            wiser_amd/csrc/score_plan.cc wiser_amd/csrc/score_docs.cc \
            wiser_amd/csrc/bool_plan.cc wiser_amd/csrc/bool_search.cc wiser_amd/csrc/count_bool.cc \
+           wiser_amd/csrc/docset.cc \
            wiser_amd/csrc/docstore.cc \
            wiser_amd/csrc/snippet.cc wiser_amd/csrc/kernels.hip
 HDRS    := $(wildcard wiser_amd/csrc/*.h) include/wiser_hip.h
@@ -34,6 +35,7 @@ BOPLAN  := wiser_amd/_lib/bool_plan_check
 BOCLI   := wiser_amd/_lib/bool_cli
 COPLAN  := wiser_amd/_lib/count_plan_check
 COCLI   := wiser_amd/_lib/count_cli
+DSCLI   := wiser_amd/_lib/docset_cli
 
 # (the buffer owner's, the two plans' and the shard layout's checks are tests of those files
 # alone: a tree whose tests/ does not hold their sources still builds everything else)
@@ -46,7 +48,8 @@ all: $(LIB) $(ORACLE) $(CLI) $(CALIB) $(DICT) $(if $(wildcard tests/cpp/dev_mem_
      $(if $(wildcard tests/cpp/bool_plan_check.cc),$(BOPLAN)) \
      $(if $(wildcard tests/cpp/bool_cli.cc),$(BOCLI)) \
      $(if $(wildcard tests/cpp/count_plan_check.cc),$(COPLAN)) \
-     $(if $(wildcard tests/cpp/count_cli.cc),$(COCLI))
+     $(if $(wildcard tests/cpp/count_cli.cc),$(COCLI)) \
+     $(if $(wildcard tests/cpp/docset_cli.cc),$(DSCLI))
 
 # CPU check of the term dictionary (tests/test_dictionary.py)
 $(DICT): tests/cpp/dict_check.cc wiser_amd/csrc/index.h $(LIB)
@@ -111,6 +114,10 @@ $(BOCLI): tests/cpp/bool_cli.cc include/wiser_hip_engine.hpp include/wiser_hip.h
 # C++ host of the match-count mirror (tests/test_gpu_count.py)
 $(COCLI): tests/cpp/count_cli.cc include/wiser_hip_engine.hpp include/wiser_hip.h $(LIB)
 	$(CXX) -O2 -std=c++17 -Iinclude -o $@ tests/cpp/count_cli.cc -Lwiser_amd/_lib -lwiser_hip -Wl,-rpath,'$$ORIGIN'
+
+# C++ host of the doc-set mirror (tests/test_gpu_docset.py)
+$(DSCLI): tests/cpp/docset_cli.cc include/wiser_hip_engine.hpp include/wiser_hip.h $(LIB)
+	$(CXX) -O2 -std=c++17 -Iinclude -o $@ tests/cpp/docset_cli.cc -Lwiser_amd/_lib -lwiser_hip -Wl,-rpath,'$$ORIGIN'
 
 $(OBJDIR)/%.o: wiser_amd/csrc/% $(HDRS)
 	@mkdir -p $(OBJDIR)

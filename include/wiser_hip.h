@@ -349,6 +349,73 @@ int wsr_count_bool(wsr_handle* h, const wsr_bool_query* q, int32_t nq, int64_t* 
 int wsr_count_bool_ex(wsr_handle* h, const wsr_bool_query* q, int32_t nq, int64_t* counts,
                       int32_t item_blocks, struct wsr_or_stats* stats);
 
+/* Doc sets (beyond the reference): "only among these docs" -- a user's access
+ * list, a tenant's or a category's docs, a date range (doc ids ascend in
+ * ingestion order), search within earlier results.  Over-fetching and
+ * discarding cannot be exact: k stops at WSR_MAX_K, every ranking path prunes
+ * on a threshold built from docs the caller would discard, and a count cannot
+ * be post-filtered at all.
+ *
+ * A wsr_docset is an immutable bitmap over the doc ids [0, n_docs) of the
+ * WHOLE index (also on a doc-range shard engine), resident in HBM: bit d & 31
+ * of word d >> 5 is doc d, zero-padded to whole windows of 2,048 docs.  It
+ * remembers the handle it was made on; a set passed to any call with another
+ * handle is WSR_E_INVALID.  It is read-only after creation: any number of
+ * concurrent calls on its handle may use it.  Destroying it while a call uses
+ * it, or after wsr_close of its handle, is the caller's error.  Null
+ * arguments are WSR_E_INVALID throughout (wsr_docset_destroy ignores them).
+ *
+ * wsr_docset_from_ids: the set of docs[0 .. n), in any order, duplicates
+ * allowed; n = 0 (docs may then be NULL) gives the empty set.  An id outside
+ * [0, n_docs) of the whole index is WSR_E_INVALID and no set is created.  The
+ * bitmap is built on the host and uploaded once.
+ * wsr_docset_from_bool: the docs of the image's doc range that match q under
+ * the Match rule of wsr_search_bool, word for word; k is ignored, as in
+ * wsr_count_bool.  With `within` not NULL the result is intersected with it,
+ * so sets compose.  A query the host settles (a missing MUST term, min_should
+ * out of reach, MUST_NOT terms only, no terms) gives the empty set.  Checks
+ * and error codes are wsr_count_bool's; item_blocks is wsr_count_bool_ex's
+ * (0: the engine's default).  On a doc-range shard engine no bit outside the
+ * image's doc range is set.
+ * wsr_docset_count: *n = the number of docs in the set.
+ * wsr_docset_ids: the set's doc ids in ascending order.  *n receives the
+ * number needed; when *n > cap nothing is written to out and the call returns
+ * WSR_E_LIMIT (out may be NULL when cap is 0).  A device-to-host copy and a
+ * host expansion.
+ * wsr_docset_destroy: frees the set. */
+typedef struct wsr_docset wsr_docset;
+int wsr_docset_from_ids(wsr_handle* h, const int32_t* docs, int64_t n, wsr_docset** out);
+int wsr_docset_from_bool(wsr_handle* h, const wsr_bool_query* q, const wsr_docset* within, int32_t item_blocks,
+                         wsr_docset** out);
+int wsr_docset_count(wsr_handle* h, const wsr_docset* s, int64_t* n);
+int wsr_docset_ids(wsr_handle* h, const wsr_docset* s, int32_t* out, int64_t cap, int64_t* n);
+void wsr_docset_destroy(wsr_handle* h, wsr_docset* s);
+
+/* wsr_search_bool_ex and wsr_count_bool_ex restricted to doc sets.  filters:
+ * nq entries, filters[i] the set of query i -- a batch can carry different
+ * users' access lists; a NULL entry leaves that query unfiltered and a NULL
+ * array leaves every query unfiltered.
+ * Match.  Doc d matches query i iff it matches under wsr_search_bool's rule
+ * AND its bit is set in filters[i].  Score, ranking (RankDoc over the matching
+ * docs in ascending doc id, then SortHeap), missing terms, empty results,
+ * errors and calling conventions are wsr_search_bool_ex's and
+ * wsr_count_bool_ex's, unchanged; a set made on another handle is
+ * WSR_E_INVALID.  Every check happens before anything is enqueued and a
+ * refused call writes nothing.
+ * Identities, bit for bit and ties included: with every filter NULL, or with
+ * the set of all docs, the call gives exactly the unfiltered call's result;
+ * with the empty set it gives no hits and a count of 0.
+ * The filter is applied before the threshold, not after it: the k hits are the
+ * best k of the set's matching docs whatever else the index holds.
+ * stats: a 2,048-doc window in which the query's set holds no doc is not run
+ * and counts neither in windows nor in windows_skipped; a query whose set is
+ * empty never reaches the device. */
+int wsr_search_bool_filtered(wsr_handle* h, const wsr_bool_query* q, int32_t nq, const wsr_docset* const* filters,
+                             int32_t hit_stride, wsr_hit* hits, int32_t* n_hits, int32_t item_blocks,
+                             struct wsr_or_stats* stats);
+int wsr_count_bool_filtered(wsr_handle* h, const wsr_bool_query* q, int32_t nq, const wsr_docset* const* filters,
+                            int64_t* counts, int32_t item_blocks, struct wsr_or_stats* stats);
+
 /* Queries as text, the reference's query-log format (QueryProducerByLog,
  * query_pool.h:319-378): one query per line, terms separated by spaces, a
  * line in double quotes is a phrase query.  Every term is resolved through the

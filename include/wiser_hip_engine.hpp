@@ -65,6 +65,44 @@ inline void check(int rc) {
   if (rc != WSR_OK) throw std::runtime_error(std::string("wiser_hip: ") + wsr_last_error());
 }
 
+// A set of doc ids of the whole index resident on the device (wsr_docset;
+// VacuumHipEngine::MakeDocSet): the filter of SearchBool and CountBool.
+// Immutable; destroy it before its engine.
+class DocSet {
+ public:
+  DocSet(wsr_handle* h, wsr_docset* s) : h_(h), s_(s) {}
+  DocSet(DocSet&& o) noexcept : h_(o.h_), s_(o.s_) { o.s_ = nullptr; }
+  DocSet& operator=(DocSet&& o) noexcept {
+    if (this != &o) {
+      wsr_docset_destroy(h_, s_);
+      h_ = o.h_;
+      s_ = o.s_;
+      o.s_ = nullptr;
+    }
+    return *this;
+  }
+  DocSet(const DocSet&) = delete;
+  DocSet& operator=(const DocSet&) = delete;
+  ~DocSet() { wsr_docset_destroy(h_, s_); }
+
+  const wsr_docset* get() const { return s_; }
+  int64_t Count() const {
+    int64_t n = 0;
+    check(wsr_docset_count(h_, s_, &n));
+    return n;
+  }
+  std::vector<int32_t> Ids() const {   // ascending
+    std::vector<int32_t> out(static_cast<size_t>(Count()));
+    int64_t n = 0;
+    check(wsr_docset_ids(h_, s_, out.data(), static_cast<int64_t>(out.size()), &n));
+    return out;
+  }
+
+ private:
+  wsr_handle* h_;
+  wsr_docset* s_;
+};
+
 class VacuumHipEngine {
  public:
   // bloom_enable_factor: CreateSearchEngine's (engine_factory.h:33-34), default 1
@@ -151,30 +189,29 @@ class VacuumHipEngine {
   // and doc_freqs as for a match_any query: a term missing from the index has
   // doc_freq 0 (a missing MUST term: no entries); no terms or n_results <= 0:
   // nothing, doc_freqs unset.  The engine checks the limits.
-  std::vector<SearchResult> SearchBool(const std::vector<BoolQuery>& qs) {
+  std::vector<SearchResult> SearchBool(const std::vector<BoolQuery>& qs) { return SearchBool(qs, {}); }
+  // ... restricted to doc sets (wsr_search_bool_filtered): filters[i] is query
+  // i's set, nullptr for none; no filters at all is the call above.
+  std::vector<SearchResult> SearchBool(const std::vector<BoolQuery>& qs, const std::vector<const DocSet*>& filters) {
     std::vector<wsr_bool_query> in(qs.size());
     std::vector<std::vector<int>> freqs(qs.size());
     int stride = 1;
     for (size_t i = 0; i < qs.size(); ++i) {
       const BoolQuery& q = qs[i];
-      if (q.terms.size() > WSR_MAX_OR_TERMS)
-        throw std::runtime_error("wiser_hip: more than WSR_MAX_OR_TERMS terms in a boolean query");
       wsr_bool_query& w = in[i];
-      w = wsr_bool_query{};
-      w.n_terms = static_cast<int32_t>(q.terms.size());
+      w = Resolve(q, &freqs[i]);
       w.k = q.n_results < 0 ? 0 : q.n_results;
-      w.min_should = q.min_should;
-      for (size_t t = 0; t < q.terms.size(); ++t) {
-        int32_t df;
-        check(wsr_lookup(h_, q.terms[t].first.c_str(), &w.list_ids[t], &df));
-        w.role[t] = static_cast<uint8_t>(q.terms[t].second);
-        freqs[i].push_back(df);
-      }
       if (w.k > stride) stride = w.k;
     }
     std::vector<wsr_hit> hits(qs.size() * stride);
     std::vector<int32_t> nh(qs.size());
-    check(wsr_search_bool(h_, in.data(), static_cast<int32_t>(qs.size()), stride, hits.data(), nh.data()));
+    if (filters.empty()) {
+      check(wsr_search_bool(h_, in.data(), static_cast<int32_t>(qs.size()), stride, hits.data(), nh.data()));
+    } else {
+      const std::vector<const wsr_docset*> f = RawFilters(filters, qs.size());
+      check(wsr_search_bool_filtered(h_, in.data(), static_cast<int32_t>(qs.size()), f.data(), stride, hits.data(),
+                                     nh.data(), 0, nullptr));
+    }
     std::vector<SearchResult> out(qs.size());
     for (size_t i = 0; i < qs.size(); ++i) {
       if (qs[i].terms.empty() || in[i].k == 0) continue;
@@ -192,25 +229,36 @@ class VacuumHipEngine {
   // wsr_count_bool: how many docs match each query under SearchBool's match
   // rule.  n_results is ignored; a term missing from the index is list id -1.
   // On a doc-range shard engine: the matches in the shard's doc range.
-  std::vector<int64_t> CountBool(const std::vector<BoolQuery>& qs) {
+  std::vector<int64_t> CountBool(const std::vector<BoolQuery>& qs) { return CountBool(qs, {}); }
+  // ... restricted to doc sets (wsr_count_bool_filtered), as SearchBool's filters
+  std::vector<int64_t> CountBool(const std::vector<BoolQuery>& qs, const std::vector<const DocSet*>& filters) {
     std::vector<wsr_bool_query> in(qs.size());
-    for (size_t i = 0; i < qs.size(); ++i) {
-      const BoolQuery& q = qs[i];
-      if (q.terms.size() > WSR_MAX_OR_TERMS)
-        throw std::runtime_error("wiser_hip: more than WSR_MAX_OR_TERMS terms in a boolean query");
-      wsr_bool_query& w = in[i];
-      w = wsr_bool_query{};
-      w.n_terms = static_cast<int32_t>(q.terms.size());
-      w.min_should = q.min_should;
-      for (size_t t = 0; t < q.terms.size(); ++t) {
-        int32_t df;
-        check(wsr_lookup(h_, q.terms[t].first.c_str(), &w.list_ids[t], &df));
-        w.role[t] = static_cast<uint8_t>(q.terms[t].second);
-      }
-    }
+    for (size_t i = 0; i < qs.size(); ++i) in[i] = Resolve(qs[i], nullptr);
     std::vector<int64_t> counts(qs.size());
-    check(wsr_count_bool(h_, in.data(), static_cast<int32_t>(qs.size()), counts.data()));
+    if (filters.empty()) {
+      check(wsr_count_bool(h_, in.data(), static_cast<int32_t>(qs.size()), counts.data()));
+    } else {
+      const std::vector<const wsr_docset*> f = RawFilters(filters, qs.size());
+      check(wsr_count_bool_filtered(h_, in.data(), static_cast<int32_t>(qs.size()), f.data(), counts.data(), 0,
+                                    nullptr));
+    }
     return counts;
+  }
+
+  // wsr_docset_from_ids: the set of the given doc ids of the whole index (any
+  // order, duplicates allowed; an id outside the index is refused).
+  DocSet MakeDocSet(const std::vector<int32_t>& ids) {
+    wsr_docset* s = nullptr;
+    check(wsr_docset_from_ids(h_, ids.data(), static_cast<int64_t>(ids.size()), &s));
+    return DocSet(h_, s);
+  }
+  // wsr_docset_from_bool: the docs that match q under SearchBool's match rule
+  // (n_results is ignored), intersected with `within` when given.
+  DocSet MakeDocSet(const BoolQuery& q, const DocSet* within = nullptr) {
+    const wsr_bool_query w = Resolve(q, nullptr);
+    wsr_docset* s = nullptr;
+    check(wsr_docset_from_bool(h_, &w, within ? within->get() : nullptr, 0, &s));
+    return DocSet(h_, s);
   }
 
   std::vector<SearchResult> SearchBatch(const std::vector<SearchQuery>& qs) {
@@ -294,6 +342,29 @@ class VacuumHipEngine {
   }
 
  private:
+  // q by list ids (k left 0); freqs, when given, receives the terms' doc_freqs
+  wsr_bool_query Resolve(const BoolQuery& q, std::vector<int>* freqs) const {
+    if (q.terms.size() > WSR_MAX_OR_TERMS)
+      throw std::runtime_error("wiser_hip: more than WSR_MAX_OR_TERMS terms in a boolean query");
+    wsr_bool_query w{};
+    w.n_terms = static_cast<int32_t>(q.terms.size());
+    w.min_should = q.min_should;
+    for (size_t t = 0; t < q.terms.size(); ++t) {
+      int32_t df;
+      check(wsr_lookup(h_, q.terms[t].first.c_str(), &w.list_ids[t], &df));
+      w.role[t] = static_cast<uint8_t>(q.terms[t].second);
+      if (freqs) freqs->push_back(df);
+    }
+    return w;
+  }
+  static std::vector<const wsr_docset*> RawFilters(const std::vector<const DocSet*>& filters, size_t nq) {
+    if (filters.size() != nq) throw std::runtime_error("wiser_hip: one filter (or nullptr) per query");
+    std::vector<const wsr_docset*> f(nq, nullptr);
+    for (size_t i = 0; i < nq; ++i)
+      if (filters[i]) f[i] = filters[i]->get();
+    return f;
+  }
+
   std::string dir_;
   int device_;
   int bloom_factor_ = 1;

@@ -146,6 +146,15 @@ _sigs = {
     "wsr_count_bool": (C.c_int, [_P, C.POINTER(BoolQuery), C.c_int32, C.POINTER(C.c_int64)]),
     "wsr_count_bool_ex": (C.c_int, [_P, C.POINTER(BoolQuery), C.c_int32, C.POINTER(C.c_int64), C.c_int32,
                                     C.POINTER(OrStats)]),
+    "wsr_docset_from_ids": (C.c_int, [_P, C.POINTER(C.c_int32), C.c_int64, C.POINTER(_P)]),
+    "wsr_docset_from_bool": (C.c_int, [_P, C.POINTER(BoolQuery), _P, C.c_int32, C.POINTER(_P)]),
+    "wsr_docset_count": (C.c_int, [_P, _P, C.POINTER(C.c_int64)]),
+    "wsr_docset_ids": (C.c_int, [_P, _P, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int64)]),
+    "wsr_docset_destroy": (None, [_P, _P]),
+    "wsr_search_bool_filtered": (C.c_int, [_P, C.POINTER(BoolQuery), C.c_int32, C.POINTER(_P), C.c_int32,
+                                           C.POINTER(Hit), C.POINTER(C.c_int32), C.c_int32, C.POINTER(OrStats)]),
+    "wsr_count_bool_filtered": (C.c_int, [_P, C.POINTER(BoolQuery), C.c_int32, C.POINTER(_P),
+                                          C.POINTER(C.c_int64), C.c_int32, C.POINTER(OrStats)]),
     "wsr_resolve_text": (C.c_int, [_P, C.c_char_p, C.c_int64, C.c_int32, C.c_int32, C.POINTER(Query),
                                    C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64]),
     "wsr_search_text": (C.c_int, [_P, C.c_char_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,

@@ -96,6 +96,7 @@ struct BoolCtx {
   gpu::DevBuf<unsigned long long> d_stats;   // kNumOrStats
   gpu::DevBuf<wiser::HitDev> d_hits;
   gpu::DevBuf<int32_t> d_nhits;
+  gpu::DevBuf<const uint32_t*> d_filt;       // per query its doc set's bitmap (docset.cc; on first use)
 };
 
 // What one wsr_count_bool call holds on the device (count_bool.cc): kept in a
@@ -108,6 +109,18 @@ struct CountCtx {
   gpu::DevBuf<uint32_t> d_icnt;              // matching docs per item (sized together with d_items)
   gpu::DevBuf<uint32_t> d_ctr;               // kNumCounters (the error flags)
   gpu::DevBuf<unsigned long long> d_stats;   // kNumOrStats
+  gpu::DevBuf<const uint32_t*> d_filt;       // per query its doc set's bitmap (docset.cc; on first use)
+};
+
+// A doc set (docset.cc): a bitmap over the doc ids of the whole index, bit
+// d & 31 of word d >> 5 doc d, zero-padded to whole windows of kOrWindow docs
+// (never empty: a NULL bitmap is "unfiltered" to the kernels).  Immutable once
+// its creating call returns.
+struct wsr_docset {
+  wsr_handle* h = nullptr;        // the handle it was made on
+  gpu::DevBuf<uint32_t> bits;
+  int64_t count = 0;              // docs in the set
+  uint32_t lo = 0, hi = 0;        // every doc of the set lies in [lo, hi)
 };
 
 struct wsr_handle {

@@ -219,6 +219,24 @@ hipError_t launch_count_items(const IndexArgs& ix, const OrQuery* oq, const Bool
                               uint32_t n_items, int nt_max, uint32_t* item_count, uint32_t* counters,
                               unsigned long long* stats, hipStream_t st);
 
+// Doc-set filters (docset.cc).  A doc set is a bitmap over the whole index's
+// docs, bit d & 31 of word d >> 5 doc d, zero-padded to whole windows of
+// kOrWindow docs.  filt[i] is the set of query oq[i], NULL for none: a doc
+// matches only if its bit is set, and a window without a set doc is not run.
+// launch_bool_items_filtered is launch_bool_items with the table
+// (bool_filtered_kernel); launch_count_items_filtered is launch_count_items
+// with it (count_filtered_kernel) and, when out_bits is not NULL, also ORs
+// every matching doc's bit into that zeroed bitmap (match_set_kernel: the
+// table then describes one query).
+hipError_t launch_bool_items_filtered(const IndexArgs& ix, const OrQuery* oq, const BoolRoles* roles,
+                                      const uint32_t* const* filt, const OrItem* items, uint32_t n_items, int nt_max,
+                                      Event* events, uint32_t* ev_cnt, uint32_t* counters, unsigned long long* stats,
+                                      hipStream_t st);
+hipError_t launch_count_items_filtered(const IndexArgs& ix, const OrQuery* oq, const BoolRoles* roles,
+                                       const uint32_t* const* filt, const OrItem* items, uint32_t n_items, int nt_max,
+                                       uint32_t* item_count, uint32_t* out_bits, uint32_t* counters,
+                                       unsigned long long* stats, hipStream_t st);
+
 // Given (query, doc) pairs (wsr_score_docs): one wave per item of at most
 // kScoreLanes candidates, sorted by doc id at docs[first ..]; the answer of
 // candidate j goes to out[index[j]].  Rows no item covers are left as they are

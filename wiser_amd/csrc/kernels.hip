@@ -3540,6 +3540,15 @@ __device__ __forceinline__ uint32_t load_list_block(const IndexArgs& ix, const L
   return cnt;
 }
 
+// The bits of a doc-set word that starts at doc `base` whose docs lie in [lo, hi).
+__device__ __forceinline__ uint32_t window_word_mask(uint32_t base, uint32_t lo, uint32_t hi) {
+  const uint32_t a = lo > base ? lo - base : 0u;   // bits below a are docs below lo
+  const uint32_t b = hi > base ? hi - base : 0u;   // bits from b on are docs from hi on
+  const uint32_t below_b = b >= 32u ? 0xFFFFFFFFu : (1u << b) - 1u;
+  const uint32_t below_a = a >= 32u ? 0xFFFFFFFFu : (1u << a) - 1u;
+  return below_b & ~below_a;
+}
+
 // The windowed traversal of or_kernel (WSR_QUERY_OR) and bool_kernel
 // (wsr_search_bool): window_item<kBool>, one wave per item (a doc-id range of
 // the image, cut by the host).  The range is walked in windows of kOrWindow
@@ -3587,6 +3596,18 @@ __device__ __forceinline__ uint32_t load_list_block(const IndexArgs& ix, const L
 // docs passed to the filter, and the argument above holds whether or not the
 // doc that holds only non-essential slots matches.  MUST_NOT slots carry no
 // bound and are never essential.
+//
+// The filtered instance (kFilt, wsr_search_bool_filtered): filt[oq] is the
+// query's doc-set bitmap (bit d & 31 of word d >> 5 is doc d of the whole
+// index, zero-padded to whole windows; NULL: unfiltered), and "its bit is set"
+// is one more conjunct of the match rule.  Lane l loads word wb / 32 + l of the
+// window; a window none of whose docs in [lo, hi) is in the set is not
+// accumulated at all (it counts neither as run nor as skipped), and in the
+// touched-docs pass a doc outside the set is not valid to the filter, as a doc
+// lost to MUST_NOT.  MaxScore stays exact: theta is the k-th best of the docs
+// that matched, the doc set included, and were passed on, and the reference
+// heap over the filtered stream has seen those and more -- the argument above,
+// with "matches" read as "matches and is in the set".
 template <bool kBool>
 struct WindowHeld {
   uint32_t held[kOrWindow / 2];   // 16 bits per doc (two docs per word): bit t = slot t's list holds it
@@ -3608,16 +3629,20 @@ static_assert(sizeof(WindowLds<false>) + sizeof(WindowHeld<true>) == sizeof(Wind
 constexpr double kOrMargin = 0.998;   // the pre-probe pruning's margin
 
 // cache: per term slot the current block of its list, decoded (128 doc ids, 128 tfs)
-template <bool kBool>
+template <bool kBool, bool kFilt = false>
 __device__ __forceinline__ void window_item(WindowLds<kBool>& S, uint32_t* cache, const IndexArgs& ix,
                                             const OrQuery* __restrict__ oqs, const BoolRoles* __restrict__ roles,
                                             const OrItem* __restrict__ items, uint32_t it,
                                             Event* __restrict__ events, uint32_t* __restrict__ ev_cnt,
                                             uint32_t* __restrict__ counters,
-                                            unsigned long long* __restrict__ stats) {
+                                            unsigned long long* __restrict__ stats,
+                                            const uint32_t* const* __restrict__ filt = nullptr) {
+  static_assert(kBool || !kFilt, "window_item: the filtered instance is a boolean one");
   const uint32_t l = threadIdx.x & 63;
   const OrItem I = items[it];
   const OrQuery* Q = oqs + I.oq;
+  const uint32_t* fbits = nullptr;   // the query's doc set (uniform)
+  if constexpr (kFilt) fbits = filt[I.oq];
   const uint32_t nt = uni(static_cast<uint32_t>(Q->nt));
   const uint32_t k = uni(static_cast<uint32_t>(Q->k));
   const bool wide = k > static_cast<uint32_t>(kMaxK);   // every passing doc is an event
@@ -3731,6 +3756,16 @@ __device__ __forceinline__ void window_item(WindowLds<kBool>& S, uint32_t* cache
     }
     if (next >= dhi) break;
     const uint32_t hi = dhi - wb > kOrWindow ? wb + kOrWindow : dhi;
+    uint32_t fw = 0xFFFFFFFFu;   // this lane's word of the doc set, its docs outside [lo, hi) cleared
+    if constexpr (kFilt) {
+      if (fbits) {
+        fw = fbits[wb / 32u + l] & window_word_mask(wb + 32u * l, lo, hi);
+        if (__ballot(fw != 0u) == 0ull) {   // no doc of the window is in the set
+          pos = hi;
+          continue;
+        }
+      }
+    }
     ++n_win;
     for (uint32_t t = 0; t < nt; ++t) {
       const ListDev L = ix.lists[Q->list[t]];
@@ -3781,6 +3816,12 @@ __device__ __forceinline__ void window_item(WindowLds<kBool>& S, uint32_t* cache
         const uint32_t h = (S.held[i >> 1] >> (16u * (i & 1u))) & 0xFFFFu;
         match = touched && (h & must) == must && (h & nots) == 0u &&
                 static_cast<uint32_t>(__popc(h & should)) >= need;
+        if constexpr (kFilt) {
+          // the chunk's 64 doc-set bits, from the two lanes' words as m is
+          const uint32_t f_lo = static_cast<uint32_t>(__builtin_amdgcn_readlane(fw, static_cast<int>(2u * ch)));
+          const uint32_t f_hi = static_cast<uint32_t>(__builtin_amdgcn_readlane(fw, static_cast<int>(2u * ch + 1u)));
+          match = match && (((static_cast<uint64_t>(f_hi) << 32) | f_lo) >> l) & 1ull;
+        }
         __builtin_amdgcn_wave_barrier();   // (every lane has read its half of a held word)
         if (l < 32u) S.held[32u * ch + l] = 0u;
       }
@@ -3849,6 +3890,20 @@ __global__ __launch_bounds__(64) void bool_kernel(IndexArgs ix, const OrQuery* _
   window_item<true>(S, or_cache, ix, oqs, roles, items, blockIdx.x, events, ev_cnt, counters, stats);
 }
 
+// wsr_search_bool_filtered: bool_kernel with filt[i] the doc set of query oqs[i] (NULL: none)
+__global__ __launch_bounds__(64) void bool_filtered_kernel(IndexArgs ix, const OrQuery* __restrict__ oqs,
+                                                           const BoolRoles* __restrict__ roles,
+                                                           const uint32_t* const* __restrict__ filt,
+                                                           const OrItem* __restrict__ items, uint32_t n_items,
+                                                           Event* __restrict__ events, uint32_t* __restrict__ ev_cnt,
+                                                           uint32_t* __restrict__ counters,
+                                                           unsigned long long* __restrict__ stats) {
+  __shared__ WindowLds<true> S;
+  extern __shared__ uint32_t or_cache[];
+  if (blockIdx.x >= n_items) return;
+  window_item<true, true>(S, or_cache, ix, oqs, roles, items, blockIdx.x, events, ev_cnt, counters, stats, filt);
+}
+
 // ------------------------------------------------ exact match counts --
 // wsr_count_bool: count_kernel, one wave per item of a boolean query (the
 // items, kept slots and roles are plan_bool's; bool_plan.h, plan_count).  It
@@ -3888,21 +3943,28 @@ struct CountLds {
 static_assert(kOrWindow / 32 == 64, "count_kernel: one bitmap word per lane and slot");
 static_assert(kMaxOrTerms <= 16, "count_kernel: five planes count 0..16 SHOULD slots");
 
+// The body serves three kernels.  count_kernel has both switches off.  kFilt
+// (wsr_count_bool_filtered, wsr_docset_from_bool's `within`): filt[oq] is the
+// query's doc-set bitmap as window_item<true, true> reads it (NULL: none);
+// lane l's word of the window, its docs outside [lo, hi) cleared, is ANDed
+// into m, and a window none of whose docs in [lo, hi) is in the set is not
+// run.  Steps (1) to (4) hold with "matches" read as "matches and is in the
+// set".  kOut (wsr_docset_from_bool): m is also written out, into the zeroed
+// bitmap `out` over the whole index's docs.  Two items of one query can share
+// a window and so a word, hence the atomic OR; their bits are disjoint.
+//
 // count_cache: per slot the current block of its list, decoded (128 doc ids)
-__global__ __launch_bounds__(64) void count_kernel(IndexArgs ix, const OrQuery* __restrict__ oqs,
-                                                   const BoolRoles* __restrict__ roles,
-                                                   const OrItem* __restrict__ items, uint32_t n_items,
-                                                   uint32_t* __restrict__ item_count,
-                                                   uint32_t* __restrict__ counters,
-                                                   unsigned long long* __restrict__ stats) {
-  __shared__ CountLds S;
-  extern __shared__ uint32_t count_cache[];
-  const uint32_t it = blockIdx.x;
-  if (it >= n_items) return;
+template <bool kFilt, bool kOut>
+__device__ __forceinline__ void count_item(CountLds& S, uint32_t* count_cache, const IndexArgs& ix,
+                                           const OrQuery* oqs, const BoolRoles* roles, const OrItem* items,
+                                           uint32_t it, uint32_t* item_count, uint32_t* counters,
+                                           unsigned long long* stats, const uint32_t* const* filt, uint32_t* out) {
   const uint32_t l = threadIdx.x & 63;
   const OrItem I = items[it];
   const OrQuery* Q = oqs + I.oq;
   const BoolRoles R = roles[I.oq];
+  const uint32_t* fbits = nullptr;   // the query's doc set (uniform)
+  if constexpr (kFilt) fbits = filt[I.oq];
   const uint32_t nt = uni(static_cast<uint32_t>(Q->nt));
   const uint32_t dhi = uni(I.doc_hi);
   const uint32_t must = uni(R.must_mask), should = uni(R.should_mask), nots = uni(R.not_mask);
@@ -3967,6 +4029,16 @@ __global__ __launch_bounds__(64) void count_kernel(IndexArgs ix, const OrQuery* 
     const uint32_t wb = next & ~(kOrWindow - 1u);
     const uint32_t lo = umax(wb, pos);
     const uint32_t hi = dhi - wb > kOrWindow ? wb + kOrWindow : dhi;
+    uint32_t fw = 0xFFFFFFFFu;   // this lane's word of the doc set, its docs outside [lo, hi) cleared
+    if constexpr (kFilt) {
+      if (fbits) {
+        fw = fbits[wb / 32u + l] & window_word_mask(wb + 32u * l, lo, hi);
+        if (__ballot(fw != 0u) == 0ull) {   // no doc of the window is in the set
+          pos = hi;
+          continue;
+        }
+      }
+    }
     ++n_win;
     for (uint32_t t = 0; t < nt; ++t) {
       const ListDev L = ix.lists[Q->list[t]];
@@ -4029,7 +4101,12 @@ __global__ __launch_bounds__(64) void count_kernel(IndexArgs ix, const OrQuery* 
       }
       shouldw = gt | eq;
     }
-    n_match += __popc(mustw & ~notw & shouldw);
+    uint32_t m = mustw & ~notw & shouldw;
+    if constexpr (kFilt) m &= fw;
+    if constexpr (kOut) {
+      if (m) atomicOr(&out[wb / 32u + l], m);
+    }
+    n_match += __popc(m);
     n_touch += __popc(anyw);
     __builtin_amdgcn_wave_barrier();
     pos = hi;
@@ -4042,6 +4119,49 @@ __global__ __launch_bounds__(64) void count_kernel(IndexArgs ix, const OrQuery* 
     atomicAdd(&stats[kOrStatWindows], static_cast<unsigned long long>(n_win));
     atomicAdd(&stats[kOrStatTouched], static_cast<unsigned long long>(touched));
   }
+}
+
+__global__ __launch_bounds__(64) void count_kernel(IndexArgs ix, const OrQuery* __restrict__ oqs,
+                                                   const BoolRoles* __restrict__ roles,
+                                                   const OrItem* __restrict__ items, uint32_t n_items,
+                                                   uint32_t* __restrict__ item_count,
+                                                   uint32_t* __restrict__ counters,
+                                                   unsigned long long* __restrict__ stats) {
+  __shared__ CountLds S;
+  extern __shared__ uint32_t count_cache[];
+  if (blockIdx.x >= n_items) return;
+  count_item<false, false>(S, count_cache, ix, oqs, roles, items, blockIdx.x, item_count, counters, stats, nullptr,
+                           nullptr);
+}
+
+// wsr_count_bool_filtered: count_kernel with filt[i] the doc set of query oqs[i] (NULL: none)
+__global__ __launch_bounds__(64) void count_filtered_kernel(IndexArgs ix, const OrQuery* __restrict__ oqs,
+                                                            const BoolRoles* __restrict__ roles,
+                                                            const uint32_t* const* __restrict__ filt,
+                                                            const OrItem* __restrict__ items, uint32_t n_items,
+                                                            uint32_t* __restrict__ item_count,
+                                                            uint32_t* __restrict__ counters,
+                                                            unsigned long long* __restrict__ stats) {
+  __shared__ CountLds S;
+  extern __shared__ uint32_t count_cache[];
+  if (blockIdx.x >= n_items) return;
+  count_item<true, false>(S, count_cache, ix, oqs, roles, items, blockIdx.x, item_count, counters, stats, filt,
+                          nullptr);
+}
+
+// wsr_docset_from_bool: count_filtered_kernel that also ORs every matching doc's bit into `out`
+__global__ __launch_bounds__(64) void match_set_kernel(IndexArgs ix, const OrQuery* __restrict__ oqs,
+                                                       const BoolRoles* __restrict__ roles,
+                                                       const uint32_t* const* __restrict__ filt,
+                                                       const OrItem* __restrict__ items, uint32_t n_items,
+                                                       uint32_t* __restrict__ item_count,
+                                                       uint32_t* __restrict__ out,
+                                                       uint32_t* __restrict__ counters,
+                                                       unsigned long long* __restrict__ stats) {
+  __shared__ CountLds S;
+  extern __shared__ uint32_t count_cache[];
+  if (blockIdx.x >= n_items) return;
+  count_item<true, true>(S, count_cache, ix, oqs, roles, items, blockIdx.x, item_count, counters, stats, filt, out);
 }
 
 // One wave per OR query: the events of its items (doc-id order) through the
@@ -4181,6 +4301,32 @@ hipError_t launch_count_items(const IndexArgs& ix, const OrQuery* oq, const Bool
   if (!n_items) return hipSuccess;
   hipLaunchKernelGGL(count_kernel, dim3(n_items), dim3(64), sizeof(uint32_t) * 128u * static_cast<uint32_t>(nt_max),
                      st, ix, oq, roles, items, n_items, item_count, counters, stats);
+  return hipGetLastError();
+}
+
+hipError_t launch_bool_items_filtered(const IndexArgs& ix, const OrQuery* oq, const BoolRoles* roles,
+                                      const uint32_t* const* filt, const OrItem* items, uint32_t n_items, int nt_max,
+                                      Event* events, uint32_t* ev_cnt, uint32_t* counters, unsigned long long* stats,
+                                      hipStream_t st) {
+  if (!n_items) return hipSuccess;
+  hipLaunchKernelGGL(bool_filtered_kernel, dim3(n_items), dim3(64),
+                     sizeof(uint32_t) * 256u * static_cast<uint32_t>(nt_max), st, ix, oq, roles, filt, items, n_items,
+                     events, ev_cnt, counters, stats);
+  return hipGetLastError();
+}
+
+hipError_t launch_count_items_filtered(const IndexArgs& ix, const OrQuery* oq, const BoolRoles* roles,
+                                       const uint32_t* const* filt, const OrItem* items, uint32_t n_items, int nt_max,
+                                       uint32_t* item_count, uint32_t* out_bits, uint32_t* counters,
+                                       unsigned long long* stats, hipStream_t st) {
+  if (!n_items) return hipSuccess;
+  const size_t lds = sizeof(uint32_t) * 128u * static_cast<uint32_t>(nt_max);
+  if (out_bits)
+    hipLaunchKernelGGL(match_set_kernel, dim3(n_items), dim3(64), lds, st, ix, oq, roles, filt, items, n_items,
+                       item_count, out_bits, counters, stats);
+  else
+    hipLaunchKernelGGL(count_filtered_kernel, dim3(n_items), dim3(64), lds, st, ix, oq, roles, filt, items, n_items,
+                       item_count, counters, stats);
   return hipGetLastError();
 }
 

@@ -82,6 +82,48 @@ class SearchResult:
         return self.entries[i]
 
 
+class DocSet:
+    """A set of doc ids of the whole index, resident on the device (wsr_docset;
+    VacuumEngine.docset / docset_from_bool): the filter of search_bool and
+    count_bool.  Immutable; close() it (or use it as a context manager) before
+    its engine is closed."""
+
+    def __init__(self, engine: "VacuumEngine", handle):
+        self._engine = engine
+        self._s = handle
+
+    def count(self) -> int:
+        n = C.c_int64()
+        check(lib.wsr_docset_count(self._engine._h, self._s, C.byref(n)))
+        return n.value
+
+    def ids(self):
+        """The set's doc ids, ascending: a numpy int32 array."""
+        import numpy as np
+        out = np.empty(self.count(), dtype=np.int32)
+        n = C.c_int64()
+        check(lib.wsr_docset_ids(self._engine._h, self._s, out.ctypes.data_as(C.POINTER(C.c_int32)), out.size,
+                                 C.byref(n)))
+        return out[: n.value]
+
+    def close(self) -> None:
+        if self._s is not None and self._engine._h is not None:
+            lib.wsr_docset_destroy(self._engine._h, self._s)
+        self._s = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def ParseUrl(url: str):
     """engine_factory.h:21-31: ``vacuum:<source_type>:<path>``."""
     parts = url.split(":", 2)
@@ -270,9 +312,41 @@ class VacuumEngine:
             dfs.append(df)
         return q, (None if (not dfs or q.k == 0) else dfs)
 
-    def search_bool(self, queries: Sequence[BoolQuery]) -> List[SearchResult]:
+    # ---- doc sets -------------------------------------------------------
+    def docset(self, ids) -> DocSet:
+        """wsr_docset_from_ids: the set of the given doc ids of the whole index
+        (any order, duplicates allowed; an id outside [0, NumDocs()) is refused)."""
+        import numpy as np
+        a = np.ascontiguousarray(np.asarray(list(ids) if not hasattr(ids, "dtype") else ids, dtype=np.int64))
+        if a.size and (a.min() < -2**31 or a.max() >= 2**31):
+            raise _capi.WiserError(_capi.E_INVALID, "a doc id outside int32")
+        a = a.astype(np.int32)
+        s = C.c_void_p()
+        check(lib.wsr_docset_from_ids(self._h, a.ctypes.data_as(C.POINTER(C.c_int32)), a.size, C.byref(s)))
+        return DocSet(self, s)
+
+    def docset_from_bool(self, query: BoolQuery, within: Optional[DocSet] = None) -> DocSet:
+        """wsr_docset_from_bool: the docs that match the query under search_bool's
+        match rule (n_results is ignored), intersected with `within` when given."""
+        q = self.resolve_bool(query)[0]
+        s = C.c_void_p()
+        check(lib.wsr_docset_from_bool(self._h, C.byref(q), within._s if within is not None else None, 0,
+                                       C.byref(s)))
+        return DocSet(self, s)
+
+    @staticmethod
+    def _filter_array(filters, n):
+        """filters (one DocSet or None per query) as the C ABI's array"""
+        if len(filters) != n:
+            raise ValueError("one filter (or None) per query")
+        return (C.c_void_p * n)(*[f._s if f is not None else None for f in filters])
+
+    def search_bool(self, queries: Sequence[BoolQuery],
+                    filters: Optional[Sequence[Optional[DocSet]]] = None) -> List[SearchResult]:
         """wsr_search_bool: one SearchResult per query, entries ordered as every
-        query's, doc_freqs as for Search with match_any (0 for a missing term)."""
+        query's, doc_freqs as for Search with match_any (0 for a missing term).
+        filters (wsr_search_bool_filtered): one DocSet or None per query; a
+        query ranks only the docs of its set."""
         if not queries:
             return []
         n = len(queries)
@@ -285,7 +359,11 @@ class VacuumEngine:
             stride = max(stride, arr[i].k)
         hits = (_capi.Hit * (n * stride))()
         nh = (C.c_int32 * n)()
-        check(lib.wsr_search_bool(self._h, arr, n, stride, hits, nh))
+        if filters is None:
+            check(lib.wsr_search_bool(self._h, arr, n, stride, hits, nh))
+        else:
+            check(lib.wsr_search_bool_filtered(self._h, arr, n, self._filter_array(filters, n), stride, hits, nh,
+                                               0, None))
         out = []
         for i in range(n):
             r = SearchResult()
@@ -297,16 +375,22 @@ class VacuumEngine:
         return out
 
     # ---- exact match counts ---------------------------------------------
-    def count_bool(self, queries: Sequence[BoolQuery]) -> List[int]:
+    def count_bool(self, queries: Sequence[BoolQuery],
+                   filters: Optional[Sequence[Optional[DocSet]]] = None) -> List[int]:
         """wsr_count_bool: how many docs match each query under search_bool's
         match rule (n_results is ignored; on a doc-range shard engine, the
-        matches in the shard's doc range -- the shards of a partition add up)."""
+        matches in the shard's doc range -- the shards of a partition add up).
+        filters (wsr_count_bool_filtered): one DocSet or None per query; a
+        query counts only the docs of its set."""
         if not queries:
             return []
         n = len(queries)
         arr = (_capi.BoolQuery * n)(*[self.resolve_bool(bq)[0] for bq in queries])
         counts = (C.c_int64 * n)()
-        check(lib.wsr_count_bool(self._h, arr, n, counts))
+        if filters is None:
+            check(lib.wsr_count_bool(self._h, arr, n, counts))
+        else:
+            check(lib.wsr_count_bool_filtered(self._h, arr, n, self._filter_array(filters, n), counts, 0, None))
         return list(counts)
 
     def count(self, query: SearchQuery) -> int:
