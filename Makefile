@@ -9,8 +9,8 @@ ORACLE  := oracle/_build/liboracle.so
 SRCS    := wiser_amd/csrc/writer.cc wiser_amd/csrc/index.cc wiser_amd/csrc/engine.cc \
            wiser_amd/csrc/shard_exchange.cc wiser_amd/csrc/batch_plan.cc wiser_amd/csrc/server.cc \
            wiser_amd/csrc/score_plan.cc wiser_amd/csrc/score_docs.cc \
-           wiser_amd/csrc/bool_plan.cc wiser_amd/csrc/bool_search.cc wiser_amd/csrc/count_bool.cc \
-           wiser_amd/csrc/docset.cc \
+           wiser_amd/csrc/bool_plan.cc wiser_amd/csrc/bool_run.cc wiser_amd/csrc/bool_search.cc \
+           wiser_amd/csrc/count_bool.cc wiser_amd/csrc/docset.cc \
            wiser_amd/csrc/docstore.cc \
            wiser_amd/csrc/snippet.cc wiser_amd/csrc/kernels.hip
 HDRS    := $(wildcard wiser_amd/csrc/*.h) include/wiser_hip.h

@@ -15,6 +15,8 @@ import pytest
 from bool_model import BoolModel
 from conftest import ROOT
 from heapmodel import rank_stream
+from test_gpu_bool import run_bool
+from test_gpu_count import run_count as run_count_ex
 from test_gpu_or import (EDGE_TERMS, _Ctx, _synth_queries, edge_ctx, skip_ctx, synth_ctx,  # noqa: F401
                          tie_ctx)
 
@@ -557,6 +559,41 @@ def test_two_threads_share_a_set(tie_ctx, tie_bm, tie_sets):   # noqa: F811
         t.join(timeout=120)
         assert not t.is_alive(), "a caller did not return"
     assert not errors, errors[:2]
+
+
+@pytest.mark.parametrize("item_blocks", [0, 1])
+def test_modes_share_contexts(tie_ctx, tie_bm, tie_sets, item_blocks):   # noqa: F811
+    """One engine, one thread: every call takes the pooled context the call
+    before it gave back, so a context sized by a count serves a larger search
+    (its tables grow, its event and hit buffers are new to it), then a match
+    set, filtered calls and a count again."""
+    eng = tie_ctx.eng
+    searches = [(t, ms, k) for t, ms in TIE_QUERIES for k in (3, 65, 1024)][:40]
+    counted = (TIE_QUERIES * 3)[:40]
+
+    def n_match(t, ms, name=None):
+        return expected(("tie", str(t), ms, "count", name),
+                        lambda: len(stream(tie_bm, t, ms, FILTER_IDS[name] if name else None)))
+
+    def top(t, ms, k, name=None):
+        return expected(("tie", str(t), ms, k, name),
+                        lambda: rank_stream(stream(tie_bm, t, ms, FILTER_IDS[name] if name else None), k)[0])
+
+    got, _ = run_count_ex(eng, counted[:3], item_blocks)
+    assert got == [n_match(t, ms) for t, ms in counted[:3]]
+    got, _ = run_bool(eng, searches, item_blocks)
+    assert got == [top(t, ms, k) for t, ms, k in searches] and any(len(g) > 64 for g in got)
+    with match_set(eng, *q("+a b"), item_blocks=item_blocks) as s:
+        want = [d for _, d in tie_bm.matching(*q("+a b"))]
+        assert s.ids().tolist() == want and s.count() == len(want) > 0
+    names = ["third", None, "range", "empty", "full"]
+    got, _ = run_count(eng, TIE_QUERIES[:5], [tie_sets[n] if n else None for n in names], item_blocks)
+    assert got == [n_match(t, ms, n) for (t, ms), n in zip(TIE_QUERIES[:5], names)]
+    two = [TIE_QUERIES[1] + (10,), TIE_QUERIES[4] + (65,)]
+    got, _ = run_search(eng, two, [tie_sets["range"], tie_sets["third"]], item_blocks)
+    assert got == [top(*two[0], "range"), top(*two[1], "third")] and all(got)
+    got, _ = run_count_ex(eng, counted, item_blocks)
+    assert got == [n_match(t, ms) for t, ms in counted] and max(got) > 1024
 
 
 FIXTURE_QUERIES = {

@@ -83,33 +83,23 @@ struct ScoreCtx {
   gpu::DevBuf<wiser::DocScore> d_out;
 };
 
-// What one wsr_search_bool call holds on the device (bool_search.cc): kept in
-// a per-handle pool, one per concurrent caller, as the ScoreCtx.
+// What one boolean call holds on the device (bool_run.cc: wsr_search_bool,
+// wsr_count_bool, their filtered forms and wsr_docset_from_bool): kept in a
+// per-handle pool, one per concurrent caller, as the ScoreCtx.  The buffers a
+// search alone needs are allocated by the first search the context serves.
 struct BoolCtx {
   gpu::Stream st;
   gpu::DevBuf<wiser::OrQuery> d_qs;
   gpu::DevBuf<wiser::BoolRoles> d_roles;     // (sized together with d_qs)
   gpu::DevBuf<wiser::OrItem> d_items;
-  gpu::DevBuf<uint32_t> d_evcnt;             // (sized together with d_items)
-  gpu::DevBuf<wiser::Event> d_events;
-  gpu::DevBuf<uint32_t> d_ctr;               // kNumCounters (the error flags)
+  // per item: its events (a search) or its matching docs (a count); sized together with d_items
+  gpu::DevBuf<uint32_t> d_item_n;
+  gpu::DevBuf<uint32_t> d_ctr;              // kNumCounters (the error flags)
   gpu::DevBuf<unsigned long long> d_stats;   // kNumOrStats
+  gpu::DevBuf<const uint32_t*> d_filt;       // per query its doc set's bitmap (on first use)
+  gpu::DevBuf<wiser::Event> d_events;        // search only, as d_hits and d_nhits (on first use)
   gpu::DevBuf<wiser::HitDev> d_hits;
   gpu::DevBuf<int32_t> d_nhits;
-  gpu::DevBuf<const uint32_t*> d_filt;       // per query its doc set's bitmap (docset.cc; on first use)
-};
-
-// What one wsr_count_bool call holds on the device (count_bool.cc): kept in a
-// per-handle pool, one per concurrent caller, as the BoolCtx.
-struct CountCtx {
-  gpu::Stream st;
-  gpu::DevBuf<wiser::OrQuery> d_qs;
-  gpu::DevBuf<wiser::BoolRoles> d_roles;     // (sized together with d_qs)
-  gpu::DevBuf<wiser::OrItem> d_items;
-  gpu::DevBuf<uint32_t> d_icnt;              // matching docs per item (sized together with d_items)
-  gpu::DevBuf<uint32_t> d_ctr;               // kNumCounters (the error flags)
-  gpu::DevBuf<unsigned long long> d_stats;   // kNumOrStats
-  gpu::DevBuf<const uint32_t*> d_filt;       // per query its doc set's bitmap (docset.cc; on first use)
 };
 
 // A doc set (docset.cc): a bitmap over the doc ids of the whole index, bit
@@ -170,8 +160,7 @@ struct wsr_handle {
   int lean_wgs_two = 0; // ... its two-term instance's (one workgroup per CU past residency)
   int gen_cap = 0;     // general workgroups launched at most
   CtxPool<ScoreCtx> score_pool;         // wsr_score_docs' reusable contexts
-  CtxPool<BoolCtx> bool_pool;           // wsr_search_bool's
-  CtxPool<CountCtx> count_pool;         // wsr_count_bool's
+  CtxPool<BoolCtx> bool_pool;           // the boolean calls' (bool_run.cc)
   // what the upload plan (batch_plan.h) reads of the handle
   wiser::ImageView view() const {
     wiser::ImageView v;

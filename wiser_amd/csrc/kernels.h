@@ -203,39 +203,31 @@ hipError_t launch_or_replay(const OrQuery* oq, uint32_t n_or, const OrItem* item
 // instantiated with, per doc of the window, the set of slots that held it; a
 // touched doc reaches the item's running top-k (or its event slot, k > kMaxK) only if it satisfies roles[q]
 // (engine_types.h, BoolRoles).  oq[i] and roles[i] describe one query; the
-// events are replayed by launch_or_replay over the same oq table.
-hipError_t launch_bool_items(const IndexArgs& ix, const OrQuery* oq, const BoolRoles* roles, const OrItem* items,
-                             uint32_t n_items, int nt_max, Event* events, uint32_t* ev_cnt, uint32_t* counters,
-                             unsigned long long* stats, hipStream_t st);
+// events are replayed by launch_or_replay over the same oq table.  filt: NULL
+// (bool_kernel), or the call's doc-set table (bool_filtered_kernel): filt[i]
+// is the set of query oq[i], NULL for none -- a bitmap over the whole index's
+// docs, bit d & 31 of word d >> 5 doc d, zero-padded to whole windows of
+// kOrWindow docs; a doc matches only if its bit is set, and a window without
+// a set doc is not run.
+hipError_t launch_bool_items(const IndexArgs& ix, const OrQuery* oq, const BoolRoles* roles,
+                             const uint32_t* const* filt, const OrItem* items, uint32_t n_items, int nt_max,
+                             Event* events, uint32_t* ev_cnt, uint32_t* counters, unsigned long long* stats,
+                             hipStream_t st);
 
-// Exact match counts (wsr_count_bool): count_kernel, one wave per item of
-// plan_count's tables (oq[i] and roles[i] as for launch_bool_items; k, ubsum
-// and the items' event slots are not read).  item_count[i] = matching docs of
-// item i's range; every item of the launch is written.  counters: the error
+// Exact match counts (wsr_count_bool): one wave per item of plan_count's
+// tables (oq[i], roles[i] and filt as for launch_bool_items; k, ubsum and the
+// items' event slots are not read).  item_count[i] = matching docs of item
+// i's range; every item of the launch is written.  counters: the error
 // flags; stats: kNumOrStats u64 (zeroed by the caller), of which items,
 // windows and touched docs are counted.  nt_max sizes the decoded-block cache
-// in LDS (128 doc ids per slot).
-hipError_t launch_count_items(const IndexArgs& ix, const OrQuery* oq, const BoolRoles* roles, const OrItem* items,
-                              uint32_t n_items, int nt_max, uint32_t* item_count, uint32_t* counters,
+// in LDS (128 doc ids per slot).  out_bits not NULL: match_set_kernel, which
+// also ORs every matching doc's bit into that zeroed bitmap (filt is then a
+// table, of NULLs if need be, and describes one query); else filt not NULL:
+// count_filtered_kernel; else count_kernel.
+hipError_t launch_count_items(const IndexArgs& ix, const OrQuery* oq, const BoolRoles* roles,
+                              const uint32_t* const* filt, const OrItem* items, uint32_t n_items, int nt_max,
+                              uint32_t* item_count, uint32_t* out_bits, uint32_t* counters,
                               unsigned long long* stats, hipStream_t st);
-
-// Doc-set filters (docset.cc).  A doc set is a bitmap over the whole index's
-// docs, bit d & 31 of word d >> 5 doc d, zero-padded to whole windows of
-// kOrWindow docs.  filt[i] is the set of query oq[i], NULL for none: a doc
-// matches only if its bit is set, and a window without a set doc is not run.
-// launch_bool_items_filtered is launch_bool_items with the table
-// (bool_filtered_kernel); launch_count_items_filtered is launch_count_items
-// with it (count_filtered_kernel) and, when out_bits is not NULL, also ORs
-// every matching doc's bit into that zeroed bitmap (match_set_kernel: the
-// table then describes one query).
-hipError_t launch_bool_items_filtered(const IndexArgs& ix, const OrQuery* oq, const BoolRoles* roles,
-                                      const uint32_t* const* filt, const OrItem* items, uint32_t n_items, int nt_max,
-                                      Event* events, uint32_t* ev_cnt, uint32_t* counters, unsigned long long* stats,
-                                      hipStream_t st);
-hipError_t launch_count_items_filtered(const IndexArgs& ix, const OrQuery* oq, const BoolRoles* roles,
-                                       const uint32_t* const* filt, const OrItem* items, uint32_t n_items, int nt_max,
-                                       uint32_t* item_count, uint32_t* out_bits, uint32_t* counters,
-                                       unsigned long long* stats, hipStream_t st);
 
 // Given (query, doc) pairs (wsr_score_docs): one wave per item of at most
 // kScoreLanes candidates, sorted by doc id at docs[first ..]; the answer of

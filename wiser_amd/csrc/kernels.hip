@@ -4286,47 +4286,37 @@ hipError_t launch_or_items(const IndexArgs& ix, const OrQuery* oq, const OrItem*
   return hipGetLastError();
 }
 
-hipError_t launch_bool_items(const IndexArgs& ix, const OrQuery* oq, const BoolRoles* roles, const OrItem* items,
-                             uint32_t n_items, int nt_max, Event* events, uint32_t* ev_cnt, uint32_t* counters,
-                             unsigned long long* stats, hipStream_t st) {
+hipError_t launch_bool_items(const IndexArgs& ix, const OrQuery* oq, const BoolRoles* roles,
+                             const uint32_t* const* filt, const OrItem* items, uint32_t n_items, int nt_max,
+                             Event* events, uint32_t* ev_cnt, uint32_t* counters, unsigned long long* stats,
+                             hipStream_t st) {
   if (!n_items) return hipSuccess;
-  hipLaunchKernelGGL(bool_kernel, dim3(n_items), dim3(64), sizeof(uint32_t) * 256u * static_cast<uint32_t>(nt_max),
-                     st, ix, oq, roles, items, n_items, events, ev_cnt, counters, stats);
+  const size_t lds = sizeof(uint32_t) * 256u * static_cast<uint32_t>(nt_max);
+  if (filt)
+    hipLaunchKernelGGL(bool_filtered_kernel, dim3(n_items), dim3(64), lds, st, ix, oq, roles, filt, items, n_items,
+                       events, ev_cnt, counters, stats);
+  else
+    hipLaunchKernelGGL(bool_kernel, dim3(n_items), dim3(64), lds, st, ix, oq, roles, items, n_items, events, ev_cnt,
+                       counters, stats);
   return hipGetLastError();
 }
 
-hipError_t launch_count_items(const IndexArgs& ix, const OrQuery* oq, const BoolRoles* roles, const OrItem* items,
-                              uint32_t n_items, int nt_max, uint32_t* item_count, uint32_t* counters,
+hipError_t launch_count_items(const IndexArgs& ix, const OrQuery* oq, const BoolRoles* roles,
+                              const uint32_t* const* filt, const OrItem* items, uint32_t n_items, int nt_max,
+                              uint32_t* item_count, uint32_t* out_bits, uint32_t* counters,
                               unsigned long long* stats, hipStream_t st) {
   if (!n_items) return hipSuccess;
-  hipLaunchKernelGGL(count_kernel, dim3(n_items), dim3(64), sizeof(uint32_t) * 128u * static_cast<uint32_t>(nt_max),
-                     st, ix, oq, roles, items, n_items, item_count, counters, stats);
-  return hipGetLastError();
-}
-
-hipError_t launch_bool_items_filtered(const IndexArgs& ix, const OrQuery* oq, const BoolRoles* roles,
-                                      const uint32_t* const* filt, const OrItem* items, uint32_t n_items, int nt_max,
-                                      Event* events, uint32_t* ev_cnt, uint32_t* counters, unsigned long long* stats,
-                                      hipStream_t st) {
-  if (!n_items) return hipSuccess;
-  hipLaunchKernelGGL(bool_filtered_kernel, dim3(n_items), dim3(64),
-                     sizeof(uint32_t) * 256u * static_cast<uint32_t>(nt_max), st, ix, oq, roles, filt, items, n_items,
-                     events, ev_cnt, counters, stats);
-  return hipGetLastError();
-}
-
-hipError_t launch_count_items_filtered(const IndexArgs& ix, const OrQuery* oq, const BoolRoles* roles,
-                                       const uint32_t* const* filt, const OrItem* items, uint32_t n_items, int nt_max,
-                                       uint32_t* item_count, uint32_t* out_bits, uint32_t* counters,
-                                       unsigned long long* stats, hipStream_t st) {
-  if (!n_items) return hipSuccess;
+  if (out_bits && !filt) return hipErrorInvalidValue;   // (match_set_kernel reads filt[q] unasked)
   const size_t lds = sizeof(uint32_t) * 128u * static_cast<uint32_t>(nt_max);
   if (out_bits)
     hipLaunchKernelGGL(match_set_kernel, dim3(n_items), dim3(64), lds, st, ix, oq, roles, filt, items, n_items,
                        item_count, out_bits, counters, stats);
-  else
+  else if (filt)
     hipLaunchKernelGGL(count_filtered_kernel, dim3(n_items), dim3(64), lds, st, ix, oq, roles, filt, items, n_items,
                        item_count, counters, stats);
+  else
+    hipLaunchKernelGGL(count_kernel, dim3(n_items), dim3(64), lds, st, ix, oq, roles, items, n_items, item_count,
+                       counters, stats);
   return hipGetLastError();
 }
 
