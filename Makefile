@@ -27,6 +27,7 @@ CALIB   := wiser_amd/_lib/calib_ea
 DICT    := wiser_amd/_lib/dict_check
 DEVMEM  := wiser_amd/_lib/dev_mem_check
 BPLAN   := wiser_amd/_lib/batch_plan_check
+TPLAN   := wiser_amd/_lib/tiny_plan_check
 SLAYOUT := wiser_amd/_lib/shard_layout_check
 SPLAN   := wiser_amd/_lib/score_plan_check
 SCLI    := wiser_amd/_lib/score_cli
@@ -41,6 +42,7 @@ DSCLI   := wiser_amd/_lib/docset_cli
 # alone: a tree whose tests/ does not hold their sources still builds everything else)
 all: $(LIB) $(ORACLE) $(CLI) $(CALIB) $(DICT) $(if $(wildcard tests/cpp/dev_mem_check.cc),$(DEVMEM)) \
      $(if $(wildcard tests/cpp/batch_plan_check.cc),$(BPLAN)) \
+     $(if $(wildcard tests/cpp/tiny_plan_check.cc),$(TPLAN)) \
      $(if $(wildcard tests/cpp/shard_layout_check.cc),$(SLAYOUT)) \
      $(if $(wildcard tests/cpp/score_plan_check.cc),$(SPLAN)) \
      $(if $(wildcard tests/cpp/score_cli.cc),$(SCLI)) \
@@ -70,6 +72,13 @@ $(BPLAN): tests/cpp/batch_plan_check.cc wiser_amd/csrc/batch_plan.cc wiser_amd/c
           wiser_amd/csrc/engine_types.h include/wiser_hip.h
 	@mkdir -p wiser_amd/_lib
 	$(CXX) -O2 -std=c++17 -Wall -o $@ tests/cpp/batch_plan_check.cc wiser_amd/csrc/batch_plan.cc
+
+# CPU check of the tiny class in the upload plan (tests/test_tiny_plan.py): no HIP, no engine
+$(TPLAN): tests/cpp/tiny_plan_check.cc wiser_amd/csrc/batch_plan.cc wiser_amd/csrc/batch_plan.h \
+          wiser_amd/csrc/or_plan.h \
+          wiser_amd/csrc/engine_types.h include/wiser_hip.h
+	@mkdir -p wiser_amd/_lib
+	$(CXX) -O2 -std=c++17 -Wall -o $@ tests/cpp/tiny_plan_check.cc wiser_amd/csrc/batch_plan.cc
 
 # CPU check of the shard exchange's region layout and its two device views (tests/test_shard_layout.py):
 # no HIP, no engine

@@ -151,8 +151,8 @@ int wsr_highlight(const int32_t* pairs, const int32_t* counts, int32_t n_terms, 
 
 /* Per-batch counters of the last run (for the roofline / profiles). */
 typedef struct wsr_batch_stats {
-  uint64_t work_items;       /* segments processed */
-  uint64_t survivors;        /* docs in every list (scored) */
+  uint64_t work_items;       /* segments processed (a tiny query: one) */
+  uint64_t survivors;        /* docs in every list (scored; a tiny query's matches included) */
   uint64_t driver_blocks;    /* 128-posting blocks decoded from driver lists */
   uint64_t other_blocks;     /* blocks decoded from the other lists */
   uint64_t algo_bytes;       /* sum over queries of docid+tf span bytes of its lists (a phrase
@@ -170,6 +170,10 @@ typedef struct wsr_batch_stats {
                                 postings in the image's doc range, none of which passed the score
                                 bound: what skipping whole blocks on a per-block impact maximum
                                 could leave out at most */
+  uint64_t tiny_queries;     /* queries of the tiny class (two terms, k <= 64, both lists one decoded
+                                VInts block in the image), run by tiny_kernel: each counts as one
+                                work item, its matches as survivors and events; its two blocks are
+                                not in driver_blocks / other_blocks (nothing is decoded) */
 } wsr_batch_stats;
 
 /* HBM bytes of an engine's image, per buffer. */

@@ -72,7 +72,8 @@ class BatchStats(C.Structure):
                 ("algo_bytes", C.c_uint64), ("plan_ms", C.c_double),
                 ("segment_ms", C.c_double), ("replay_ms", C.c_double),
                 ("events", C.c_uint64), ("max_query_events", C.c_uint64),
-                ("lean_ms", C.c_double), ("skippable_blocks", C.c_uint64)]
+                ("lean_ms", C.c_double), ("skippable_blocks", C.c_uint64),
+                ("tiny_queries", C.c_uint64)]
 
 
 class OrStats(C.Structure):

@@ -51,7 +51,7 @@ int plan_upload(const ImageView& v, const wsr_query* q, int32_t nq, int32_t stri
   BatchClass c;
   c.two_conj = c.two_ph = c.one_conj = true;   // (every ...: until a query says otherwise)
   // blocks of the driver lists per class: what the three persistent grids can have to run
-  uint64_t lean_need = 0, lean_need_ph = 0, gen_need = 0;
+  uint64_t lean_need = 0, lean_need_ph = 0, gen_need = 0, gen_need_rest = 0;
   const int32_t n_lists = static_cast<int32_t>(v.n_lists);
   std::vector<int32_t> ids;
   for (int i = 0; i < nq; ++i) {
@@ -137,6 +137,12 @@ int plan_upload(const ImageView& v, const wsr_query* q, int32_t nq, int32_t stri
     }
     const bool lean = is_lean_query(others_by_bitmap, d.n_terms, d.flags);
     (lean ? (phrase ? lean_need_ph : lean_need) : gen_need) += nbmin;
+    // the tiny class of a plain run (the device's rule: it comes first there)
+    const bool tiny = d.n_terms == 2 &&
+                      is_tiny_query(d.n_terms, d.flags, d.k, is_tiny_list(v.lists[ids[0]].nblk, v.lists[ids[0]].tail),
+                                    is_tiny_list(v.lists[ids[1]].nblk, v.lists[ids[1]].tail));
+    if (tiny) ++c.n_tiny;
+    else if (!lean) gen_need_rest += nbmin;
     c.gen_phrase = c.gen_phrase || (phrase && !lean);
     // every term's docid+tf span, and for a phrase query also its
     // position box (the bags the position check reads from)
@@ -156,6 +162,7 @@ int plan_upload(const ImageView& v, const wsr_query* q, int32_t nq, int32_t stri
     return static_cast<int>(std::max<uint64_t>(1, std::min<uint64_t>(cap, need)));
   };
   c.seg_grid = grid(v.gen_cap, gen_need);
+  c.seg_grid_rest = grid(v.gen_cap, gen_need_rest);
   c.lean_wgs = grid(c.two_conj ? v.lean_wgs_two : v.lean_wgs, (lean_need + kLeanWaves - 1) / kLeanWaves);
   c.lean_wgs_ph = grid(v.lean_wgs_ph, (lean_need_ph + kLeanWaves - 1) / kLeanWaves);
   c.n_or = static_cast<int>(p.orq.size());

@@ -54,6 +54,11 @@ struct BatchClass {
   uint32_t or_items = 0;
   int or_nt_max = 0;             // the most resolved terms of one of them
   uint64_t algo_static = 0;      // sum of list spans + k*12 over the uploaded queries
+  // the tiny class (is_tiny_query), which only a plain run has (launches_of):
+  // has_gen, seg_grid and the lean grids above count a tiny query in its other
+  // class, as a shard step runs it
+  int n_tiny = 0;                // tiny queries
+  int seg_grid_rest = 0;         // general workgroups over those
 };
 
 struct UploadPlan {
@@ -87,12 +92,24 @@ int plan_upload(const ImageView& v, const wsr_query* q, int32_t nq, int32_t stri
 // everything (their owners read every query's emission), and a carried owner
 // replay rides in the conjunctive launch, which runs then even with no
 // conjunctive lean item of its own.
+// A plain run (no shard step, no carried owner replay) has the tiny class
+// (tiny_class): the device plan takes the tiny queries out of the other two
+// classes, tiny_kernel is launched when the host counted any (tiny), and the
+// general launch is sized by the general queries that are left (gen_grid
+// workgroups; which batches launch it is the rule above, unchanged).  A plain
+// run whose host count is zero keeps the class on, so that a tiny query the
+// device plan finds all the same is flagged (kErrClass), not run elsewhere.
 struct Launches {
   bool conj = true, gen = true;
+  bool tiny = false;        // tiny_kernel is launched
+  int gen_grid = 0;         // general workgroups of the launch (gen)
+  bool tiny_class = false;  // the device plan classes tiny queries
 };
 constexpr Launches launches_of(const BatchClass& c, bool shard_step, bool carries_owner_replay) {
+  const bool cls = !shard_step && !carries_owner_replay;
   return Launches{shard_step || carries_owner_replay || !c.has_phrase || c.has_conj_lean,
-                  shard_step || !c.has_phrase || c.has_gen};
+                  shard_step || !c.has_phrase || c.has_gen, cls && c.n_tiny > 0,
+                  cls ? c.seg_grid_rest : c.seg_grid, cls};
 }
 
 }  // namespace wiser

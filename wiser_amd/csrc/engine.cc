@@ -510,6 +510,7 @@ int wsr_batch_create(wsr_handle* h, int32_t max_q, int32_t stride, wsr_batch** o
     b->d_hits.alloc(static_cast<size_t>(max_q) * stride);
     b->d_nhits.alloc(max_q);
     b->d_qdone.alloc(max_q);
+    b->d_tinyq.alloc(2 * static_cast<size_t>(max_q));
     b->d_stats.alloc(static_cast<size_t>(kStatStride) *
                      (std::max(std::max(h->grid, h->gen_cap), 1) +   // (seg_grid <= gen_cap)
                       kLeanWaves * (std::max(h->lean_wgs_two, 1) + std::max(h->lean_wgs_ph, 1))));
@@ -652,12 +653,14 @@ int batch_run(wsr_handle* h, wsr_batch* b, const EmitView* se, const OwnerJob* o
     pa.seg_cap = b->seg_cap;
     // (which persistent kernels a batch with phrase queries launches: launches_of, batch_plan.h)
     b->launched = launches_of(c, se != nullptr, oj != nullptr);
-    const bool run_conj = b->launched.conj, run_gen = b->launched.gen;
+    const bool run_conj = b->launched.conj, run_gen = b->launched.gen, run_tiny = b->launched.tiny;
+    const int seg_grid = b->launched.gen_grid;   // (<= c.seg_grid, which places the statistics rows)
     HIP_OK(launch_plan(pa, b->d_q(), b->nq, b->d_plan, b->d_ctr, b->d_events.size(),
                        static_cast<uint32_t>(std::min<uint64_t>(b->d_evcnt.size(), 0xFFFFFFFFull)),
                        run_conj ? kLeanWaves * c.lean_wgs : 0,
                        c.has_phrase ? kLeanWaves * c.lean_wgs_ph : 0,
-                       run_gen ? c.seg_grid : 0, fr, b->d_itemq, b->d_pub, b->d_desc, b->d_part, st));
+                       run_gen ? seg_grid : 0, b->launched.tiny_class ? c.n_tiny : -1, b->d_tinyq, fr, b->d_itemq, b->d_pub,
+                       b->d_desc, b->d_part, st));
     HIP_OK(hipEventRecord(b->ev[1], st));
     // general items on the second stream, lean items here; both drain their
     // own queue, then the streams join
@@ -665,8 +668,12 @@ int batch_run(wsr_handle* h, wsr_batch* b, const EmitView* se, const OwnerJob* o
     HIP_OK(hipStreamWaitEvent(b->st2, b->fork, 0));
     if (run_gen)
       HIP_OK(launch_segments(h->args, b->d_q(), b->d_plan, b->nq, b->d_ctr, b->d_events, b->d_evcnt,
-                             b->d_stats, c.seg_grid, fr, b->d_itemq, b->d_pub,
+                             b->d_stats, seg_grid, fr, b->d_itemq, b->d_pub,
                              c.gen_phrase ? b->d_ph : nullptr, b->st2));
+    // the tiny queries beside them: one wave each, results written in place
+    if (run_tiny)
+      HIP_OK(launch_tiny(h->args, b->d_q(), b->d_ctr, b->d_tinyq, static_cast<uint32_t>(b->max_q), c.n_tiny,
+                         b->d_hits, b->stride, b->d_nhits, b->st2));
     uint32_t* lean_stats = b->d_stats + static_cast<size_t>(kStatStride) * c.seg_grid;
     HIP_OK(hipEventRecord(b->join, b->st2));
     if (c.has_phrase) {
@@ -844,12 +851,24 @@ int wsr_batch_stats_get(wsr_handle* h, wsr_batch* b, wsr_batch_stats* out) {
     for (int i = 0; i < rows; ++i) {
       // (rows of a kernel the last run did not launch hold an earlier run's values)
       const bool conj_row = i >= b->cls.seg_grid && i < b->cls.seg_grid + kLeanWaves * b->cls.lean_wgs;
-      if (i < b->cls.seg_grid ? !b->launched.gen : (conj_row && !b->launched.conj)) continue;
+      if (i < b->cls.seg_grid ? !(b->launched.gen && i < b->launched.gen_grid) : (conj_row && !b->launched.conj))
+        continue;
       // (the third word: a general workgroup's other-list blocks, a lean wave's skippable blocks)
       sv += ws[kStatStride * i]; db += ws[kStatStride * i + 1];
       (i < b->cls.seg_grid ? ob : sk) += ws[kStatStride * i + 2];
     }
-    out->work_items = ctr[kCtrItems];
+    out->work_items = ctr[kCtrItems] + ctr[kCtrTiny];
+    out->tiny_queries = ctr[kCtrTiny];
+    // the tiny queries' matches (tiny_kernel keeps no statistics row: every match is scored and
+    // handed to the heap, so it is a survivor and an event)
+    uint64_t tiny_ev = 0, tiny_mx = 0;
+    {
+      const size_t nt = std::min<size_t>(ctr[kCtrTiny], static_cast<size_t>(b->max_q));
+      std::vector<uint32_t> tc(nt);
+      if (nt) HIP_OK(hipMemcpy(tc.data(), b->d_tinyq.get() + b->max_q, nt * sizeof(uint32_t), hipMemcpyDeviceToHost));
+      for (uint32_t n : tc) { tiny_ev += n; tiny_mx = std::max<uint64_t>(tiny_mx, n); }
+    }
+    sv += tiny_ev;
     out->survivors = sv;
     out->driver_blocks = db;
     out->other_blocks = ob;
@@ -861,7 +880,7 @@ int wsr_batch_stats_get(wsr_handle* h, wsr_batch* b, wsr_batch_stats* out) {
       std::vector<QueryPlan> pl(b->nq);
       if (items) HIP_OK(hipMemcpy(ec.data(), b->d_evcnt, items * sizeof(uint32_t), hipMemcpyDeviceToHost));
       if (b->nq) HIP_OK(hipMemcpy(pl.data(), b->d_plan, pl.size() * sizeof(QueryPlan), hipMemcpyDeviceToHost));
-      uint64_t tot = 0, mx = 0;
+      uint64_t tot = tiny_ev, mx = tiny_mx;
       for (const QueryPlan& p : pl) {
         uint64_t e = 0;
         for (uint32_t r = 0; r < p.n_items && p.item_base + r < items; ++r) e += ec[p.item_base + r];

@@ -249,6 +249,7 @@ struct wsr_batch {
   gpu::DevBuf<wiser::HitDev> d_hits;
   gpu::DevBuf<int32_t> d_nhits;
   gpu::DevBuf<uint32_t> d_qdone;   // fused replay: completed items per query
+  gpu::DevBuf<uint32_t> d_tinyq;   // the tiny list: max_q query indices, then each entry's match count
   gpu::DevBuf<uint64_t> d_pub;     // per item score floor
   gpu::DevBuf<uint32_t> d_stats;   // per general workgroup, then per lean wave: survivors, blocks
   gpu::DevBuf<uint32_t> d_ph;      // phrase scratch, gen_cap * kPhraseScratch (lazily)

@@ -201,6 +201,16 @@ constexpr bool is_phrase_query(int32_t n_terms, int32_t flags) { return n_terms 
 constexpr bool is_lean_query(bool others_by_bitmap, int32_t n_terms, int32_t flags) {
   return others_by_bitmap && !(n_terms > 2 && (flags & kQueryPhrase));
 }
+// Tiny (tiny_kernel; the rule comes before the other two): a conjunctive
+// query of two terms with k <= kMaxK whose lists are each, in this image, one
+// VInts block, which the loader has decoded (ListDev::tail): two sorted arrays
+// of at most 127 doc ids, met by one wave with no directory and no decode.
+// Only plain runs have the class: in a shard step, and in a run that carries
+// an owner replay, these queries stay with the other two classes.
+constexpr bool is_tiny_list(uint32_t nblk, uint64_t tail) { return nblk == 1 && tail != kNoTail; }
+constexpr bool is_tiny_query(int32_t n_terms, int32_t flags, int32_t k, bool tiny_list0, bool tiny_list1) {
+  return n_terms == 2 && !(flags & kQueryPhrase) && k <= kMaxK && tiny_list0 && tiny_list1;
+}
 
 // Positions of one posting list in the image (phrase queries).  The list's
 // position cozy box (flash_engine_dumper.h:78-104: full packs of 128 entries,

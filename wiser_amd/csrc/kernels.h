@@ -57,24 +57,29 @@ struct IndexArgs {
 };
 
 // counters[] (zeroed before every batch): 0 total items, 2 event capacity used,
-// 4 error flags, 6 end of the lean items, 8 end of the conjunctive lean items
+// 4 error flags, 6 end of the lean items, 8 end of the conjunctive lean items,
+// 10 entries of the batch's tiny list
 // (items [0, lean conj) run in lean_kernel's conjunctive instance, [lean
 // conj, lean) -- the lean phrase queries' -- in its phrase instance, the rest
 // in segment_kernel); each work queue has one head per XCD-sized shard, each
 // on its own 64-byte line (kCtrHead0 + 16*s lean conjunctive, kCtrPHead0 +
 // 16*s lean phrase, kCtrGHead0 + 16*s general), so the dequeues of the
-// persistent workers do not serialise on a single line.
-enum { kCtrItems = 0, kCtrEvCap = 2, kCtrError = 4, kCtrLean = 6, kCtrLeanConj = 8, kCtrHead0 = 16,
+// persistent workers do not serialise on a single line.  A tiny query has no
+// item: plan_query_kernel appends it to the batch's tiny list (kCtrTiny
+// entries, in no particular order), which tiny_kernel's plain grid runs.
+enum { kCtrItems = 0, kCtrEvCap = 2, kCtrError = 4, kCtrLean = 6, kCtrLeanConj = 8, kCtrTiny = 10, kCtrHead0 = 16,
        kQueueShards = 8,
        kCtrPHead0 = kCtrHead0 + 16 * kQueueShards,
        kCtrGHead0 = kCtrPHead0 + 16 * kQueueShards,
        kNumCounters = kCtrGHead0 + 16 * kQueueShards };
 // QueryPlan::driver = driver slot | cost bucket << kPlanBucketShift | kPlanLean
-// (| kPlanPhrase: a lean phrase query, the phrase instance's items)
+// (| kPlanPhrase: a lean phrase query, the phrase instance's items), or
+// kPlanTiny alone: a tiny query (is_tiny_query, engine_types.h)
 constexpr uint32_t kPlanSlotMask = 0x7FFu;   // (kMaxQueryTerms <= 2048)
 constexpr int kPlanBucketShift = 12;
 constexpr uint32_t kPlanLean = 1u << 16;
 constexpr uint32_t kPlanPhrase = 1u << 17;
+constexpr uint32_t kPlanTiny = 1u << 18;
 static_assert(kMaxQueryTerms <= static_cast<int>(kPlanSlotMask) + 1, "driver slot field");
 // per-workgroup statistics written by the segment kernels (no atomics):
 // stats[wg * kStatStride + {0 survivors, 1 driver blocks, 2 other blocks}]
@@ -142,8 +147,9 @@ struct FusedReplay {
 // Plan pass 1 -> pass 2: per plan workgroup (kPlanThreads queries), its items
 // per item key (class, cost bucket) and its event capacity.
 constexpr int kPlanThreads = 256;
+constexpr int kPlanKeys = 3 * kCostBuckets;   // classes: lean conjunctive, lean phrase, general
 struct PlanPart {
-  uint32_t items[3 * kCostBuckets];
+  uint32_t items[kPlanKeys];
   uint64_t cap;
 };
 
@@ -151,11 +157,23 @@ struct PlanPart {
 // has no phrase query)
 constexpr int kPhraseScratch = kMaxPhraseTerms * 256;
 
-// plan queries (2 launches); part: per plan workgroup of kPlanThreads queries
+// plan queries (2 launches); part: per plan workgroup of kPlanThreads queries;
+// tiny_grid: the tiny queries the host counted, for which it launches
+// tiny_kernel (< 0: the run has no tiny class, its queries stay lean or
+// general); tiny_q: the batch's tiny list, which pass 1 fills (the queries'
+// indices, at least nq words)
 hipError_t launch_plan(const IndexArgs& ix, const QueryIn* q, int nq, QueryPlan* plan,
                        uint32_t* counters, uint64_t ev_capacity, uint32_t item_capacity,
-                       int lean_grid, int lean_grid_ph, int seg_grid, const FusedReplay& fr, uint32_t* item_q,
-                       uint64_t* pub, QueryDesc* desc, PlanPart* part, hipStream_t st);
+                       int lean_grid, int lean_grid_ph, int seg_grid, int tiny_grid, uint32_t* tiny_q,
+                       const FusedReplay& fr, uint32_t* item_q, uint64_t* pub, QueryDesc* desc, PlanPart* part,
+                       hipStream_t st);
+// The tiny queries of a plain run (is_tiny_query), one wave each, n_tiny waves
+// at least: both decoded tails met in the wave, every match scored and handed
+// in doc order to the restated heap; hits and n_hits are written here.
+// tiny_q: cap query indices (the plan's list), then cap words that receive
+// each entry's match count.
+hipError_t launch_tiny(const IndexArgs& ix, const QueryIn* q, const uint32_t* counters, uint32_t* tiny_q,
+                       uint32_t cap, int n_tiny, HitDev* hits, int hit_stride, int32_t* n_hits, hipStream_t st);
 hipError_t launch_segments(const IndexArgs& ix, const QueryIn* q, const QueryPlan* plan, int nq,
                            uint32_t* counters, Event* events, uint32_t* ev_cnt, uint32_t* stats,
                            int grid, const FusedReplay& fr, const uint32_t* item_q,

@@ -453,7 +453,10 @@ __device__ __forceinline__ const int32_t* qlist_of(const QueryIn* qs, int qi) {
 // persistent workers take the long items first and the short ones fill the
 // tail (longest-first list scheduling).  The first bucket holds the items of
 // queries of kHeavyQueryItems items or more, whose replays are the longest.
-constexpr int kPlanKeys = 3 * kCostBuckets;   // classes: lean conjunctive, lean phrase, general
+// A tiny query (kPlanTiny) has no item: pass 1 appends it to the batch's tiny
+// list, which tiny_kernel's plain grid runs, so pass 2 knows nothing of it
+// but the count.
+// (kPlanKeys, kernels.h: the classes lean conjunctive, lean phrase and general by cost bucket)
 __device__ __forceinline__ uint32_t plan_key(uint32_t drv) {
   const uint32_t bucket = (drv >> kPlanBucketShift) & 0xFu;
   const uint32_t cls = (drv & kPlanLean) ? ((drv & kPlanPhrase) ? 1u : 0u) : 2u;
@@ -524,7 +527,8 @@ __global__ __launch_bounds__(kPlanThreads) void plan_query_kernel(IndexArgs ix, 
                                                          int nq, QueryPlan* __restrict__ plan,
                                                          uint32_t* __restrict__ counters, FusedReplay fr,
                                                          QueryDesc* __restrict__ desc,
-                                                         PlanPart* __restrict__ part) {
+                                                         PlanPart* __restrict__ part,
+                                                         uint32_t* __restrict__ tiny_q) {
   __shared__ ScanLds<kPlanKeys> S;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   QueryPlan p{0, 0, 1, 0, 0};
@@ -545,6 +549,7 @@ __global__ __launch_bounds__(kPlanThreads) void plan_query_kernel(IndexArgs ix, 
     uint32_t d = 0, nd = 0xFFFFFFFFu, o1 = kNoSlot, min_last = 0xFFFFFFFFu;
     float cost = 1.0f;
     bool lean = true;
+    bool tl0 = false, tl1 = false;   // the first two lists are tiny ones (is_tiny_list)
     if (nt <= kMaxTerms) {
       uint32_t nb[kMaxTerms], last[kMaxTerms];
       bool dn[kMaxTerms];
@@ -561,6 +566,8 @@ __global__ __launch_bounds__(kPlanThreads) void plan_query_kernel(IndexArgs ix, 
           nb[s] = L.nblk;
           dn[s] = L.bm != kNoDense;
           last[s] = L.last;
+          if (s == 0) tl0 = is_tiny_list(L.nblk, L.tail);
+          if (s == 1) tl1 = is_tiny_list(L.nblk, L.tail);
         }
       }
 #pragma unroll
@@ -600,7 +607,11 @@ __global__ __launch_bounds__(kPlanThreads) void plan_query_kernel(IndexArgs ix, 
     }
     // (so far: every other list probed by bitmap)
     lean = is_lean_query(lean, nt, q.flags);
-    if (ok) {
+    if (ok && tiny_q && is_tiny_query(nt, q.flags, q.k, tl0, tl1)) {
+      // no item, no event slot, no record: tiny_kernel reads the query and its
+      // two lists (it is appended to the tiny list below)
+      p.driver = kPlanTiny;
+    } else if (ok) {
       uint32_t seg = static_cast<uint32_t>(kSegCost / cost);
       seg = seg > ix.seg_cap ? ix.seg_cap : seg;
       if (nt == 1) seg *= kSingleWindows;   // (single_segment: windows of 64 blocks)
@@ -674,6 +685,20 @@ __global__ __launch_bounds__(kPlanThreads) void plan_query_kernel(IndexArgs ix, 
       }
     }
   }
+  // The wave's tiny queries go to the batch's tiny list: one atomic per wave
+  // takes their places (the list's order is of no consequence: every entry is
+  // a query of its own, answered into its own hit row).  At most nq entries,
+  // which the list holds (engine.cc: one per query of the batch at most).
+  {
+    const uint64_t tm = __ballot((p.driver & kPlanTiny) != 0);
+    if (tm) {   // (wave-uniform)
+      uint32_t at = 0;
+      if ((threadIdx.x & 63) == static_cast<uint32_t>(__builtin_ctzll(tm)))
+        at = atomicAdd(&counters[kCtrTiny], static_cast<uint32_t>(__popcll(tm)));
+      at = __builtin_amdgcn_readlane(at, __builtin_ctzll(tm));
+      if (p.driver & kPlanTiny) tiny_q[at + __popcll(tm & lanemask_lt())] = static_cast<uint32_t>(i);
+    }
+  }
   // the workgroup's items per key and event capacity (pass 2 scans them)
   const uint32_t key = plan_key(p.driver);
   uint32_t v[kPlanKeys], ex[kPlanKeys], tot[kPlanKeys];
@@ -699,7 +724,7 @@ __global__ __launch_bounds__(kPlanThreads) void plan_fill_kernel(int nq, QueryPl
                                                         uint32_t* __restrict__ counters,
                                                         uint64_t ev_capacity, uint32_t item_capacity,
                                                         uint32_t lean_grid, uint32_t lean_grid_ph,
-                                                        uint32_t seg_grid,
+                                                        uint32_t seg_grid, uint32_t tiny_grid,
                                                         uint32_t* __restrict__ item_q,
                                                         uint64_t* __restrict__ pub,
                                                         QueryDesc* __restrict__ desc) {
@@ -804,7 +829,11 @@ __global__ __launch_bounds__(kPlanThreads) void plan_fill_kernel(int nq, QueryPl
       // a class whose kernel the host did not launch (grid 0: its restatement
       // of the class rule found no such query) must hold no item: loud if it does
       if ((lean_grid == 0 && n_conj > 0) || (lean_grid_ph == 0 && n_lean > n_conj) ||
-          (seg_grid == 0 && total_items > n_lean))
+          (seg_grid == 0 && total_items > n_lean) ||
+          // pass 1's count of tiny queries against the host's, which sizes tiny_kernel's plain
+          // grid (0: none launched).  A run without the class (a shard step, a carried owner
+          // replay) classes no query tiny, so nothing is compared there.
+          counters[kCtrTiny] > tiny_grid)
         atomicOr(&counters[kCtrError], static_cast<uint32_t>(kErrClass));
       counters[kCtrItems] = fits ? total_items : 0u;  // never write past the workspace
       counters[kCtrLean] = fits ? n_lean : 0u;
@@ -3242,6 +3271,90 @@ __global__ __launch_bounds__(64, kSegWaves) void segment_kernel(IndexArgs ix, co
   }
 }
 
+// ----------------------------------------------------------- tiny kernel --
+// A tiny query (is_tiny_query, engine_types.h): both lists are one decoded
+// VInts block, so the whole query is two sorted arrays of at most 127 doc ids
+// that the image already holds as words.  One wave per query, a plain grid
+// over the plan's tiny list: the query, its two list heads and both tails (docs and
+// tfs, two per lane: values l and l + 64) are loaded with the driver's
+// doc-length codes; a pair whose doc ranges do not meet ends there.  Else the
+// second list's ids go to LDS, every doc of the first (the driver by the
+// plan's rule: the first of equals) in the image's doc range is looked up by
+// a lower bound, and the matches are scored in query-term order with
+// segment_kernel's operations and handed, in doc order, to the restated heap
+// (HeapSink: the heap's own test is the insertion test, so every match may
+// be offered, as for a wide query).  No directory, no decode, no event slot,
+// no hand-off: the wave writes the query's hits itself.
+constexpr int kTinyWaves = 4;   // queries per workgroup (independent waves)
+__global__ __launch_bounds__(64 * kTinyWaves) void tiny_kernel(IndexArgs ix, const QueryIn* __restrict__ qs,
+                                                               const uint32_t* __restrict__ counters,
+                                                               const uint32_t* __restrict__ tiny_q,
+                                                               uint32_t* __restrict__ tiny_cnt, uint32_t cap,
+                                                               HitDev* __restrict__ hits, int hit_stride,
+                                                               int32_t* __restrict__ n_hits) {
+  __shared__ uint32_t s_b[kTinyWaves][128];
+  const uint32_t l = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const uint32_t w = blockIdx.x * kTinyWaves + wv;
+  // (the grid is the host's count, rounded up; cap: the entries the list holds)
+  if (w >= uni(counters[kCtrTiny]) || w >= cap) return;
+  const uint32_t qi = uni(tiny_q[w]);   // entry w of the plan's tiny list; its matches go to tiny_cnt[w]
+  const uint32_t k = uni(static_cast<uint32_t>(qs[qi].k));
+  const ListDev A = ix.lists[uni(static_cast<uint32_t>(qs[qi].list[0]))];
+  const ListDev B = ix.lists[uni(static_cast<uint32_t>(qs[qi].list[1]))];
+  const uint32_t na = uni(A.tail_cnt), nb = uni(B.tail_cnt);   // (<= 127: one VInts block each)
+  const uint32_t* ta = ix.tails + A.tail;
+  const uint32_t* tb = ix.tails + B.tail;
+  const uint8_t* pl = ix.plen + static_cast<uint64_t>(A.blk0) * 128u;
+  const bool i0 = l < na, i1 = l + 64 < na, j0 = l < nb, j1 = l + 64 < nb;
+  const uint32_t a0 = i0 ? ta[l] : 0xFFFFFFFFu, a1 = i1 ? ta[l + 64] : 0xFFFFFFFFu;
+  const uint32_t fa0 = i0 ? ta[na + l] : 0u, fa1 = i1 ? ta[na + l + 64] : 0u;
+  const uint32_t b0 = j0 ? tb[l] : 0xFFFFFFFFu, b1 = j1 ? tb[l + 64] : 0xFFFFFFFFu;
+  const uint32_t fb0 = j0 ? tb[nb + l] : 0u, fb1 = j1 ? tb[nb + l + 64] : 0u;
+  const uint32_t c0 = i0 ? pl[l] : 0u, c1 = i1 ? pl[l + 64] : 0u;
+  HitDev* out = hits + static_cast<int64_t>(qi) * hit_stride;
+  // the two doc ranges (the first ids from the tails, the last from the heads)
+  const uint32_t af = __builtin_amdgcn_readlane(a0, 0), bf = __builtin_amdgcn_readlane(b0, 0);
+  if (af > B.last || bf > A.last) {
+    if (l == 0) {
+      n_hits[qi] = 0;
+      tiny_cnt[w] = 0;
+    }
+    return;
+  }
+  s_b[wv][l] = b0;
+  s_b[wv][l + 64] = b1;
+  __builtin_amdgcn_wave_barrier();
+  const bool al0 = i0 && a0 >= ix.doc_lo && a0 < ix.doc_hi;
+  const bool al1 = i1 && a1 >= ix.doc_lo && a1 < ix.doc_hi;
+  const uint32_t p0 = al0 ? lds_lower_bound(s_b[wv], nb, a0) : 0u;
+  const uint32_t p1 = al1 ? lds_lower_bound(s_b[wv], nb, a1) : 0u;
+  const bool h0 = al0 && p0 < nb && s_b[wv][p0] == a0;
+  const bool h1 = al1 && p1 < nb && s_b[wv][p1] == a1;
+  const uint32_t n_match = __popcll(__ballot(h0)) + __popcll(__ballot(h1));
+  if (l == 0) tiny_cnt[w] = n_match;
+  if (n_match == 0) {
+    if (l == 0) n_hits[qi] = 0;
+    return;
+  }
+  // the matched postings' tfs of the second list, from the lanes that hold them
+  const uint32_t x00 = __shfl(fb0, static_cast<int>(p0 & 63), 64), x01 = __shfl(fb1, static_cast<int>(p0 & 63), 64);
+  const uint32_t x10 = __shfl(fb0, static_cast<int>(p1 & 63), 64), x11 = __shfl(fb1, static_cast<int>(p1 & 63), 64);
+  const uint32_t t0 = p0 < 64 ? x00 : x01, t1 = p1 < 64 ? x10 : x11;
+  // BM25 in query-term order, the norm by the driver posting's doc-length code (as segment_kernel)
+  const double nrm0 = ix.cache[(al0 && a0 < ix.n_c4) ? c0 : 0u];
+  const double nrm1 = ix.cache[(al1 && a1 < ix.n_c4) ? c1 : 0u];
+  double s0 = 0.0, s1 = 0.0;
+  s0 += bm25_term(A.idf, fa0, nrm0);
+  s1 += bm25_term(A.idf, fa1, nrm1);
+  s0 += bm25_term(B.idf, t0, nrm0);
+  s1 += bm25_term(B.idf, t1, nrm1);
+  // values 0..63 come before values 64..127 in doc order: two chunks in lane order
+  HeapSink sink;
+  sink.k = k;
+  sink.step(s0, static_cast<int32_t>(a0), h0, [](double, int32_t) {});
+  sink.step(s1, static_cast<int32_t>(a1), h1, [](double, int32_t) {});
+  sink.finish(out, &n_hits[qi]);
+}
 
 // (below, with the owner replay kernel)
 __device__ __noinline__ void owner_replay_tail(const QueryIn* qs, const int32_t* meta, const Event* recv,
@@ -4335,14 +4448,24 @@ hipError_t launch_or_replay(const OrQuery* oq, uint32_t n_or, const OrItem* item
 
 hipError_t launch_plan(const IndexArgs& ix, const QueryIn* q, int nq, QueryPlan* plan,
                        uint32_t* counters, uint64_t ev_capacity, uint32_t item_capacity,
-                       int lean_grid, int lean_grid_ph, int seg_grid, const FusedReplay& fr, uint32_t* item_q,
-                       uint64_t* pub, QueryDesc* desc, PlanPart* part, hipStream_t st) {
+                       int lean_grid, int lean_grid_ph, int seg_grid, int tiny_grid, uint32_t* tiny_q,
+                       const FusedReplay& fr, uint32_t* item_q, uint64_t* pub, QueryDesc* desc, PlanPart* part,
+                       hipStream_t st) {
   const int n_part = std::max(1, (nq + kPlanThreads - 1) / kPlanThreads);
   hipLaunchKernelGGL(plan_query_kernel, dim3(n_part), dim3(kPlanThreads), 0, st, ix, q, nq, plan,
-                     counters, fr, desc, part);
+                     counters, fr, desc, part, tiny_grid >= 0 ? tiny_q : nullptr);
   hipLaunchKernelGGL(plan_fill_kernel, dim3(n_part), dim3(kPlanThreads), 0, st, nq, plan, part, n_part,
                      counters, ev_capacity, item_capacity, static_cast<uint32_t>(lean_grid),
-                     static_cast<uint32_t>(lean_grid_ph), static_cast<uint32_t>(seg_grid), item_q, pub, desc);
+                     static_cast<uint32_t>(lean_grid_ph), static_cast<uint32_t>(seg_grid),
+                     static_cast<uint32_t>(std::max(tiny_grid, 0)), item_q, pub, desc);
+  return hipGetLastError();
+}
+
+hipError_t launch_tiny(const IndexArgs& ix, const QueryIn* q, const uint32_t* counters, uint32_t* tiny_q,
+                       uint32_t cap, int n_tiny, HitDev* hits, int hit_stride, int32_t* n_hits, hipStream_t st) {
+  if (n_tiny <= 0) return hipSuccess;
+  hipLaunchKernelGGL(tiny_kernel, dim3((n_tiny + kTinyWaves - 1) / kTinyWaves), dim3(64 * kTinyWaves), 0, st, ix, q,
+                     counters, tiny_q, tiny_q + cap, cap, hits, hit_stride, n_hits);
   return hipGetLastError();
 }
 
